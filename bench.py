@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SDPA forward throughput on MI355X (BASELINE.json metric), 1 / 2 / 4 / 8 GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts N ranks ITSELF (fresh child processes, spawned before this process imports torch or
 touches a GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, RCCL through torch.distributed "nccl");
@@ -184,6 +184,31 @@ def cpu_baseline(cores: int):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, tensors: dict) -> None:
+    """`--dump-outputs DIR`: each tensor as DIR/<name>.npy in float32 (the inputs are seeded, so two builds can be compared
+    output for output).  A tensor that would take the files past 64 MB in all is replaced by a fixed, seeded sample of its
+    elements (flat indices from numpy's default_rng(0), sorted) and written as <name>_sample.npy beside <name>_sample_index.npy."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes <= budget:
+            np.save(d / f"{name}.npy", a)
+            budget -= a.nbytes
+            continue
+        n = max(1, min(a.size, budget // 12))  # float32 value + int64 index per sampled element
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+        np.save(d / f"{name}_sample.npy", a.reshape(-1)[idx])
+        np.save(d / f"{name}_sample_index.npy", idx.astype(np.int64))
+        budget -= n * 12
+
+
 def run_rank(args) -> None:
     import torch
     import torch.distributed as dist
@@ -336,6 +361,8 @@ def run_rank(args) -> None:
     # RCCL collectives are launched eagerly (not captured): the N > 1 headline is an eager region
     dt, settle = timed(step, args.steps, args.warmup, graph=(world == 1 and not args.no_graph))
     kernel_name = umfa_torch.last_kernel()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"o": out})  # O of the last timed step: what a caller of the in-stream entry receives
     gathered_ok = None
     if strong_ok and rank == 0:
         # the assembled tensor is the full O: rank 0 recomputes its own first chunk and the first chunk of the LAST rank with
@@ -882,6 +909,8 @@ def main() -> None:
                          "every fa_fwd16_w64 dispatch of the process is then a FLUX launch)")
     ap.add_argument("--causal", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch the K timed steps eagerly instead of as one hipGraph")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the headline's output of its last step (fp32 O) "
+                         "as DIR/<name>.npy: at most 64 MB, inputs seeded, so two builds can be compared output for output")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
