@@ -365,6 +365,26 @@ mfa_error_t umfa_attention_backward_stream(mfa_context_t context, void* stream, 
                                            int32_t intermediate_precision, bool grads_in_input_type,
                                            bool out_in_input_type);
 
+/* MI355X extra: umfa_attention_backward_stream with the mask of the forward call (the reference's backward takes none,
+ * metal_sdpa_backend.cpp:1798-1803).  (mask, mask_shape, mask_strides, mask_ndim, mask_type, mask_scalar_type) exactly as
+ * umfa_attention_forward_stream takes them: bool / fp32 / fp16 / bf16 of <= 4 dims broadcast onto [B, H, Sq, Skv] with any
+ * strides, or UMFA_MASK_TYPE_WINDOW with {left, right} in mask_shape and no tensor; `causal` combines with either.
+ * MFA_MASK_TYPE_NONE is umfa_attention_backward_stream.  16-bit operands at head_dim 64 / 128 / 256 with 16-bit
+ * intermediates run the masked MFMA backward (tiles the mask closes entirely are skipped); other calls up to head_dim 256
+ * the fp32-exact one; beyond 256: MFA_ERROR_INVALID_ARGS.  A row whose forward LSE is -inf (nothing visible) gets a zero
+ * dQ row and adds nothing to dK / dV.  Tensor masks take a per-call tile-flag pass whose scratch grows on first use;
+ * under stream capture without a warm-up call it cannot grow and the call returns MFA_ERROR_MEMORY_ALLOCATION. */
+mfa_error_t umfa_attention_backward_masked_stream(mfa_context_t context, void* stream, const void* dout, const void* q,
+                                                  const void* k, const void* v, const void* out, const float* softmax_lse,
+                                                  void* dq, void* dk, void* dv, float* d_buffer, uint32_t batch_size,
+                                                  uint32_t seq_len_q, uint32_t seq_len_kv, uint32_t num_heads,
+                                                  uint16_t head_dim, float softmax_scale, bool causal,
+                                                  int32_t input_precision, int32_t intermediate_precision,
+                                                  bool grads_in_input_type, bool out_in_input_type, const void* mask,
+                                                  const int64_t* mask_shape, const int64_t* mask_strides,
+                                                  uint32_t mask_ndim, mfa_mask_type_t mask_type,
+                                                  mfa_mask_scalar_t mask_scalar_type);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

@@ -1,5 +1,6 @@
 // fa_bwd.hip -- SDPA backward for gfx950 (dense, contiguous BHSD).  mfa_attention_backward takes no mask
-// (maskBuffer: nil, MFABridge.swift:3265); mfa_quantized_backward may pass a dense fp32 additive one.
+// (maskBuffer: nil, MFABridge.swift:3265); mfa_quantized_backward may pass a dense fp32 additive one, and
+// umfa_attention_backward_masked_stream any mask the forward reads (strided bool / fp32 / fp16 / bf16, or a window).
 //
 // Replaces the two Metal dispatches behind MultiHeadAttention.backward (MFABridge.swift:3253-3266:
 // "backward query" then "backward key-value") plus its host-side zeroing of the D scratch:
@@ -69,8 +70,9 @@ __global__ __launch_bounds__(256) void bwd_dq_kernel(BwdParams p) {
         doreg[ks] = ok ? load_as_float(p.dout, qbase + (int64_t)q_row * D + d, p.dout_prec) : 0.0f;
     }
     const float c = p.scale * UMFA_LOG2E;
-    // rows beyond Sq: L2 = +inf -> P = 0
-    const float L2 = qok ? p.lse[(int64_t)bh * p.Sq + q_row] * UMFA_LOG2E : INFINITY;
+    // rows beyond Sq: L2 = +inf -> P = 0; so for a row whose every key is masked (LSE -inf)
+    float L2 = qok ? p.lse[(int64_t)bh * p.Sq + q_row] * UMFA_LOG2E : INFINITY;
+    if (L2 == -INFINITY) L2 = INFINITY;
     const float delta = qok ? p.dvec[(int64_t)bh * p.Sq + q_row] : 0.0f;
 
     f32x16 acc[NDB];
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void bwd_dq_kernel(BwdParams p) {
         for (int r = 0; r < 16; ++r) {
             const uint32_t key = t * 32 + acc_row(r, hi);
             float arg = s[r] * c - L2;
-            if (p.mask && qok && key < p.Skv) arg += p.mask[((int64_t)bh * p.Sq + q_row) * p.Skv + key] * UMFA_LOG2E;
+            if (p.mask_kind != MK_NONE && qok && key < p.Skv) arg += bwd_mask_term(p, bh, q_row, key);
             float pr = exp2f(arg);
             if (key >= p.Skv || (p.causal && key > q_row)) pr = 0.0f;
             s[r] = pr * (dp[r] - delta);  // dS^T (without the softmax scale)
@@ -166,7 +168,8 @@ __global__ __launch_bounds__(256) void bwd_dkdv_kernel(BwdParams p) {
         load_tile_f32<DP>(dOs, p.dout, qbase, t * 32, p.Sq, D, p.dout_prec, tid);
         if (tid < 32) {
             const uint32_t row = t * 32 + tid;
-            Ls[tid] = row < p.Sq ? p.lse[(int64_t)bh * p.Sq + row] * UMFA_LOG2E : INFINITY;
+            const float l2 = row < p.Sq ? p.lse[(int64_t)bh * p.Sq + row] * UMFA_LOG2E : INFINITY;
+            Ls[tid] = l2 == -INFINITY ? INFINITY : l2;  // a fully masked row: P = 0
             Ds[tid] = row < p.Sq ? p.dvec[(int64_t)bh * p.Sq + row] : 0.0f;
         }
         __syncthreads();
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(256) void bwd_dkdv_kernel(BwdParams p) {
             const int qi = acc_row(r, hi);
             const uint32_t qrow = t * 32 + qi;
             float arg = s[r] * c - Ls[qi];
-            if (p.mask && kok && qrow < p.Sq) arg += p.mask[((int64_t)bh * p.Sq + qrow) * p.Skv + key] * UMFA_LOG2E;
+            if (p.mask_kind != MK_NONE && kok && qrow < p.Sq) arg += bwd_mask_term(p, bh, qrow, key);
             float pr = exp2f(arg);
             if (p.causal && key > qrow) pr = 0.0f;
             s[r] = pr;

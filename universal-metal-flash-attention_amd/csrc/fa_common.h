@@ -145,7 +145,7 @@ struct BwdParams {
     float* dv;
     float* dvec;
     float* rowc;    // bwd16 only, internal scratch [2][B*H*Sq]: -LSE * log2(e), then -D (written by bwd16_dq, read by bwd16_dkdv)
-    const float* mask;  // optional fp32 additive [B,H,Sq,Skv] (quantised backward only)
+    const void* mask;   // optional, read through ms[] / mask_kind as the forward's (the quantised backward's dense fp32 [B,H,Sq,Skv] is MK_F32)
     uint32_t B, H, Sq, Skv, D;
     float scale;
     int causal;
@@ -166,7 +166,24 @@ struct BwdParams {
                           // [0] 2^(eq+ek) onto the softmax scale, [1] 2^(edo+ev+ek) onto dQ, [2] 2^(edo+ev+eq) onto dK, [3] 2^edo onto dV,
                           // [4] 2^-ev onto the D the kernels subtract from dP, [5] 2^edo onto the D vector that leaves, [6] 2^-(edo+ev) onto a
                           // D vector that comes in (bwd16_rowc_kernel).  dS = P (dP - D), rounded to fp16, is then bounded by 8 head_dim.
+    // mask descriptor, as FwdParams: element strides of (b, h, q, k), 0 = broadcast; mask_kind MK_* (MK_NONE = no mask); MK_WINDOW has
+    // no tensor (win_left / win_right).  Tile flags (masked bwd16 only, optional): mask_flags_kernel's bytes, FwdParams::mask_flags.
+    int64_t ms[4];
+    int mask_kind;
+    uint32_t win_left, win_right;
+    const uint8_t* mask_flags;
+    uint32_t mf_bs, mf_hs, mf_nrb, mf_ntiles;
 };
+
+// the quantised backward ABI's mask: dense fp32 additive [B, H, Sq, Skv]
+inline void bwd_dense_f32_mask(BwdParams& p, const void* mask) {
+    p.mask = mask;
+    p.mask_kind = mask ? MK_F32 : MK_NONE;
+    p.ms[3] = 1;
+    p.ms[2] = p.Skv;
+    p.ms[1] = (int64_t)p.Sq * p.Skv;
+    p.ms[0] = (int64_t)p.H * p.Sq * p.Skv;
+}
 
 __device__ __forceinline__ float unit_c(const BwdParams& p) { return p.units ? p.units[0] : 1.0f; }
 __device__ __forceinline__ float unit_dq(const BwdParams& p) { return p.units ? p.units[1] : 1.0f; }
@@ -207,6 +224,13 @@ __device__ __forceinline__ float mask_term(const void* mask, int64_t idx, int ki
 // MK_WINDOW term of (row, key)
 __device__ __forceinline__ float window_term(uint32_t row, uint32_t key, uint32_t left, uint32_t right) {
     return (key + left >= row && key <= row + right) ? 0.0f : -INFINITY;
+}
+
+// mask term of (row, key) of (batch, head) slab bh for the backward kernels: tensor masks through the strides, windows arithmetically
+__device__ __forceinline__ float bwd_mask_term(const BwdParams& p, uint32_t bh, uint32_t row, uint32_t key) {
+    if (p.mask_kind == MK_WINDOW) return window_term(row, key, p.win_left, p.win_right);
+    const int64_t idx = (int64_t)(bh / p.H) * p.ms[0] + (int64_t)(bh % p.H) * p.ms[1] + (int64_t)row * p.ms[2] + (int64_t)key * p.ms[3];
+    return mask_term(p.mask, idx, p.mask_kind);
 }
 
 // key index inside a 32-key block held by accumulator register r of lane-half hi

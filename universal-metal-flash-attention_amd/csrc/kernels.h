@@ -33,7 +33,8 @@ struct Tuning {
         cbal_delta{-1} /* ... key tiles by which a pair's folding part is shorter than half; < 0 = the plan's choice */,
         sync_chunks{1} /* synchronous forward / backward on host-wrapping buffers: head chunks whose upload / kernels / download overlap on side streams (pinned host ranges); 1 = never (the default: one upload, the kernels, one download on the null stream), 0 = by size, n = n chunks.  OPT-IN: one of three runs of tools/lab/sync_chunk_stress.py (pin / unpin per call under heap churn, torch in-process) aborted, profiles/r6/lab_notes.md section 24 */,
         sync_chunked_calls{0} /* read-out for tests: synchronous forwards that took the chunked form */,
-        mirror_cache_hits{0} /* read-out for tests: host wrappers whose HBM mirror came from the cache of destroyed wrappers' mirrors (runtime_internal.h MirrorCache) */;
+        mirror_cache_hits{0} /* read-out for tests: host wrappers whose HBM mirror came from the cache of destroyed wrappers' mirrors (runtime_internal.h MirrorCache) */,
+        no_bwd_mask{0} /* A/B: masked training goes back to torch (read by the Python routing; the masked backward entry itself still works) */;
 };
 Tuning& tuning();
 bool set_tuning(const char* name, const char* value);  // false: unknown name or value out of range
@@ -84,6 +85,10 @@ hipError_t launch_fwd_w64(const FwdParams& p, float* part_buf, uint32_t* part_cn
 hipError_t launch_bwd(const BwdParams& p, hipStream_t stream, const char** name);
 bool bwd_16_supported(const BwdParams& p);
 hipError_t launch_bwd_16(const BwdParams& p, hipStream_t stream, const char** name);
+// ... with a mask or a sliding window (fa_bwd_16_mask.hip): bf16 / fp16, head_dim 64 / 128 / 256, one call (phases 0), dense K / V heads.
+// p.mask_kind / ms / win_* describe the mask; p.mask_flags (optional, tensor masks) the tile flags of launch_mask_flags.
+bool bwd_16_mask_supported(const BwdParams& p);
+hipError_t launch_bwd_16_masked(const BwdParams& p, hipStream_t stream, const char** name);
 
 // Neighbours of the attention path (fa_aux.hip): rotary rotation and group-wise Hadamard transform.
 struct RopeParams {

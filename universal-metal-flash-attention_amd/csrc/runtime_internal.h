@@ -133,6 +133,7 @@ struct StreamScratch {
     GrowBuf w64;        // fa_fwd16_w64: zeroed tickets (the kernel leaves them zero), then partials
     size_t w64_cnt_bytes = 0, w64_buf_hw = 0;
     GrowBuf mflags;     // mask tile flags
+    GrowBuf bmflags;    // mask tile flags of the masked backward (its own block: a forward's flags stay intact behind it)
     GrowBuf workspace;  // quantiser output (int8 Q/K, V image, scales, fp32 copies for backward); rotated K / Q of the fused-RoPE entry
     GrowBuf v16;        // default bf16 forward: per-slab exchange words + 2^e (512 bytes per (batch, KV head), zeroed once, left zero by the cast pass),
                         // then the fp16 image of V * 2^-e (never the workspace: the RoPE entry's K lives there)
@@ -209,7 +210,7 @@ struct StreamScratch {
         qhdr.bytes = 0;
     }
     void release() {
-        split.release(); w64.release(); mflags.release(); workspace.release(); v16.release(); rowc.release(); dsbuf.release(); qhdr.release();
+        split.release(); w64.release(); mflags.release(); bmflags.release(); workspace.release(); v16.release(); rowc.release(); dsbuf.release(); qhdr.release();
         w64_cnt_bytes = 0;
         split_cnt_bytes = 0;
         v16_cnt_bytes = 0;

@@ -178,6 +178,80 @@ mfa_error_t umfa_attention_backward_stream(mfa_context_t context, void* stream, 
     return e == hipSuccess ? MFA_SUCCESS : e == hipErrorInvalidValue ? MFA_ERROR_INVALID_ARGS : MFA_ERROR_EXECUTION_FAILED;
 }
 
+// MI355X extra: umfa_attention_backward_stream with the forward's mask descriptor (include/umfa_abi.h).  16-bit operands at head_dim
+// 64 / 128 / 256: the masked MFMA backward (fa_bwd_16_mask.hip) behind a tile-flag pass for tensor masks (fa_aux.hip mask_flags_kernel,
+// scratch of this (device, stream)); everything else up to head_dim 256: the fp32-exact backward, which reads the same descriptor.
+mfa_error_t umfa_attention_backward_masked_stream(mfa_context_t context, void* stream, const void* dout, const void* q,
+                                                  const void* k, const void* v, const void* out, const float* softmax_lse,
+                                                  void* dq, void* dk, void* dv, float* d_buffer, uint32_t batch_size,
+                                                  uint32_t seq_len_q, uint32_t seq_len_kv, uint32_t num_heads,
+                                                  uint16_t head_dim, float softmax_scale, bool causal,
+                                                  int32_t input_precision, int32_t intermediate_precision,
+                                                  bool grads_in_input_type, bool out_in_input_type, const void* mask,
+                                                  const int64_t* mask_shape, const int64_t* mask_strides,
+                                                  uint32_t mask_ndim, mfa_mask_type_t mask_type,
+                                                  mfa_mask_scalar_t mask_scalar_type) {
+    if (mask_type == MFA_MASK_TYPE_NONE)
+        return umfa_attention_backward_stream(context, stream, dout, q, k, v, out, softmax_lse, dq, dk, dv, d_buffer, batch_size,
+                                              seq_len_q, seq_len_kv, num_heads, head_dim, softmax_scale, causal, input_precision,
+                                              intermediate_precision, grads_in_input_type, out_in_input_type);
+    Context* ctx = as_ctx(context);
+    if (!ctx || !dout || !q || !k || !v || !out || !softmax_lse || !dq || !dk || !dv || !d_buffer) return MFA_ERROR_INVALID_ARGS;
+    if (head_dim == 0 || head_dim > 256) return MFA_ERROR_INVALID_ARGS;  // (fa_bwd_wide takes no mask)
+    FwdParams m;  // the mask as the forward entry normalises it
+    memset(&m, 0, sizeof(m));
+    if ((int)mask_type == UMFA_MASK_TYPE_WINDOW) {
+        if (!mask_shape || mask_shape[0] < 0 || mask_shape[1] < 0) return MFA_ERROR_INVALID_ARGS;
+        m.mask_kind = MK_WINDOW;
+        m.win_left = (uint32_t)(mask_shape[0] > 0x3fffffff ? 0x3fffffff : mask_shape[0]);
+        m.win_right = (uint32_t)(mask_shape[1] > 0x3fffffff ? 0x3fffffff : mask_shape[1]);
+    } else {
+        if (!mask || !mask_shape || !mask_strides || mask_ndim == 0 || mask_ndim > 4) return MFA_ERROR_INVALID_ARGS;
+        if (!normalise_mask(mask_shape, mask_strides, mask_ndim, mask_type, mask_scalar_type, m))  // (additive bytes: no mask, as on the forward)
+            return umfa_attention_backward_stream(context, stream, dout, q, k, v, out, softmax_lse, dq, dk, dv, d_buffer, batch_size,
+                                                  seq_len_q, seq_len_kv, num_heads, head_dim, softmax_scale, causal, input_precision,
+                                                  intermediate_precision, grads_in_input_type, out_in_input_type);
+        m.mask = mask;
+    }
+    if ((size_t)batch_size * num_heads * seq_len_q * seq_len_kv == 0) return MFA_SUCCESS;
+    BwdParams p;
+    memset(&p, 0, sizeof(p));
+    p.dout = dout; p.q = q; p.k = k; p.v = v; p.o = (const float*)out; p.lse = softmax_lse;
+    p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv; p.dvec = d_buffer;
+    p.B = batch_size; p.H = num_heads; p.Sq = seq_len_q; p.Skv = seq_len_kv; p.D = head_dim;
+    p.scale = softmax_scale; p.causal = causal ? 1 : 0;
+    p.in_prec = dense_prec(input_precision); p.dout_prec = p.in_prec;
+    p.grad_in_type = grads_in_input_type ? 1 : 0;
+    p.o_in_type = (out_in_input_type && p.in_prec != P_FP32) ? 1 : 0;
+    p.mask = m.mask; p.mask_kind = m.mask_kind; p.win_left = m.win_left; p.win_right = m.win_right;
+    for (int i = 0; i < 4; ++i) p.ms[i] = m.ms[i];
+    const bool lowp = dense_prec(intermediate_precision) != P_FP32 && !tuning().bwd_exact.load(std::memory_order_relaxed);
+    const bool mfma16 = lowp && bwd_16_mask_supported(p);
+    if (grads_in_input_type && !mfma16) return MFA_ERROR_INVALID_ARGS;
+    const char* name = "none";
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const int dev = stream_device((hipStream_t)stream);
+    DeviceGuard guard(dev);
+    hipError_t e;
+    if (mfma16) {
+        StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
+        p.rowc = (float*)sc.rowc.ensure((size_t)2 * batch_size * num_heads * seq_len_q * sizeof(float), (hipStream_t)stream);
+        if (!p.rowc) return MFA_ERROR_MEMORY_ALLOCATION;
+        if (p.mask_kind != MK_WINDOW && !tuning().no_mask_flags.load(std::memory_order_relaxed)) {
+            m.B = p.B; m.H = p.H; m.Sq = p.Sq; m.Skv = p.Skv; m.D = p.D;
+            uint8_t* fl = (uint8_t*)sc.bmflags.ensure(mask_flags_bytes(m), (hipStream_t)stream);
+            if (!fl) return MFA_ERROR_MEMORY_ALLOCATION;  // (capture without a warm-up call: the block cannot grow)
+            if (launch_mask_flags(m, fl, (hipStream_t)stream) != hipSuccess) return MFA_ERROR_EXECUTION_FAILED;
+            p.mask_flags = m.mask_flags; p.mf_bs = m.mf_bs; p.mf_hs = m.mf_hs; p.mf_nrb = m.mf_nrb; p.mf_ntiles = m.mf_ntiles;
+        }
+        e = launch_bwd_16_masked(p, (hipStream_t)stream, &name);
+    } else {
+        e = launch_bwd(p, (hipStream_t)stream, &name);
+    }
+    ctx->last_kernel = name;
+    return e == hipSuccess ? MFA_SUCCESS : e == hipErrorInvalidValue ? MFA_ERROR_INVALID_ARGS : MFA_ERROR_EXECUTION_FAILED;
+}
+
 // MI355X extra: the in-stream backward for grouped-query attention WITHOUT expanded K / V (the reference's route is
 // repeat_interleave of K and V before both passes, metal_sdpa_backend.cpp:1694-1702): k, v are [B, Hkv, Skv, D]; query head
 // h reads K / V head h / (Hq / Hkv) in place; dK / dV are produced per query head in fp32 scratch and summed over each
@@ -471,7 +545,7 @@ int32_t mfa_quantized_backward(mfa_context_t context, mfa_buffer_t q, mfa_buffer
             if (e == hipErrorNotSupported) continue;  // (alignment of a wrapped caller buffer): the exact path
         } else {
             p.dout = bdo->dev; p.q = views.qf; p.k = views.kf; p.v = views.vf;
-            p.mask = bm ? (const float*)bm->dev : nullptr;
+            bwd_dense_f32_mask(p, bm ? bm->dev : nullptr);
             p.in_prec = P_FP32; p.dout_prec = prec;
             e = launch_bwd(p, stream, &name);
         }

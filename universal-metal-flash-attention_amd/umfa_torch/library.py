@@ -1,4 +1,4 @@
-"""Dispatcher-level binding of the SDPA path: `umfa::sdpa_forward` / `umfa::sdpa_backward` custom ops (fake
+"""Dispatcher-level binding of the SDPA path: `umfa::sdpa_forward` / `umfa::sdpa_backward` / `umfa::sdpa_backward_masked` custom ops (fake
 implementations + autograd registered, so torch.compile(fullgraph=True) keeps them as single graph nodes) and an opt-in
 override of `aten::scaled_dot_product_attention` for the CUDA(=ROCm) dispatch keys.
 
@@ -71,13 +71,31 @@ def _(dout, q, k, v, out, lse, is_causal, scale):
         torch.empty_like(v, memory_format=torch.contiguous_format)
 
 
+@torch.library.custom_op("umfa::sdpa_backward_masked", mutates_args=(), device_types="cuda")
+def sdpa_backward_masked(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor,
+                         lse: torch.Tensor, attn_mask: torch.Tensor, is_causal: bool,
+                         scale: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """dQ, dK, dV in the operand dtype with the forward's mask (umfa_attention_backward_masked_stream); no gradient of the mask."""
+    return ops.attention_backward(dout.to(q.dtype).contiguous(), q.contiguous(), k.contiguous(), v.contiguous(),
+                                  out.contiguous(), lse, scale=float(scale), causal=bool(is_causal), mask=attn_mask)
+
+
+@sdpa_backward_masked.register_fake
+def _(dout, q, k, v, out, lse, attn_mask, is_causal, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format), torch.empty_like(k, memory_format=torch.contiguous_format), \
+        torch.empty_like(v, memory_format=torch.contiguous_format)
+
+
 def _setup_context(ctx, inputs, output):
     q, k, v, attn_mask, is_causal, scale = inputs
     out, lse = output
-    if attn_mask is not None and (q.requires_grad or k.requires_grad or v.requires_grad):
-        raise RuntimeError("umfa::sdpa_forward: the dense backward takes no attn_mask (metal_sdpa_backend.cpp:1798-1803); "
-                           "the routing function sends masked training calls to torch's native SDPA")
-    ctx.save_for_backward(q, k, v, out, lse)
+    if attn_mask is not None and attn_mask.requires_grad and (q.requires_grad or k.requires_grad or v.requires_grad):
+        raise RuntimeError("umfa::sdpa_forward: no gradient of attn_mask is built here; "
+                           "the routing function sends training calls with a learnable mask to torch's native SDPA")
+    if attn_mask is not None:
+        ctx.save_for_backward(q, k, v, out, lse, attn_mask)  # the mask as it came in (no copy)
+    else:
+        ctx.save_for_backward(q, k, v, out, lse)
     ctx.is_causal, ctx.scale = bool(is_causal), float(scale)
     if q.requires_grad or k.requires_grad or v.requires_grad:
         # the op body (which cannot see requires_grad) counted this call as fp32_instream: move it, so that the eager and
@@ -87,8 +105,11 @@ def _setup_context(ctx, inputs, output):
 
 
 def _backward(ctx, dout, dlse):
-    q, k, v, out, lse = ctx.saved_tensors
-    dq, dk, dv = torch.ops.umfa.sdpa_backward(dout, q, k, v, out, lse, ctx.is_causal, ctx.scale)
+    q, k, v, out, lse, *m = ctx.saved_tensors
+    if m:
+        dq, dk, dv = torch.ops.umfa.sdpa_backward_masked(dout, q, k, v, out, lse, m[0], ctx.is_causal, ctx.scale)
+    else:
+        dq, dk, dv = torch.ops.umfa.sdpa_backward(dout, q, k, v, out, lse, ctx.is_causal, ctx.scale)
     return dq, dk, dv, None, None, None
 
 
@@ -112,7 +133,14 @@ def op_supports(q, k, v, attn_mask, dropout_p, needs_grad: bool, is_causal: bool
     if q.shape[3] == 0 or q.shape[3] > 1024:  # (the reference callers' limit; above 256: fa_fwd_wide / fa_bwd_wide)
         return False
     if attn_mask is not None:
-        if needs_grad or attn_mask.dtype not in (torch.bool,) + _SUPPORTED or attn_mask.dim() > 4:
+        if attn_mask.dtype not in (torch.bool,) + _SUPPORTED or attn_mask.dim() > 4:
+            return False
+        # training with a mask: where the eager routing serves it (sdpa.MASKED_TRAINING_HEAD_DIMS: 16-bit operands at head_dim 64 / 128,
+        # not a learnable mask).  (The option no_bwd_mask acts on the eager routing: it is not read while tracing.)
+        if needs_grad and (attn_mask.requires_grad or q.dtype not in (torch.float16, torch.bfloat16)
+                           or q.shape[3] not in _s.MASKED_TRAINING_HEAD_DIMS):
+            return False
+        if needs_grad and not torch.compiler.is_compiling() and ops.get_option("no_bwd_mask") != "0":
             return False
         try:
             full = (q.shape[0], q.shape[1], q.shape[2], k.shape[2])

@@ -48,7 +48,7 @@ def release_scratch(stream=None, all_streams: bool = False) -> None:
 # environment: UMFA_FORCE_W64, UMFA_W64_TAU, ...); this module only reads and writes it.
 _OPTION_NAMES = ("softmax_reference", "softmax_tau", "w64_tau", "force_w64", "no_w64", "w64_grid", "w64_skew", "no_mask_flags", "bwd_exact",
                  "bwd_dq", "bwd_persist", "bwd_separate_delta", "no_split", "force_split", "no_dma", "bn64", "pv_fp16", "bwd_ds_store", "no_w64_mask", "ksplit", "no_pipe", "no_w64_mask_lazy", "no_w64_bias", "no_w64_f32_mask", "f32_mask_ratio", "mask_pass_ratio", "no_w64_ragged_mask", "no_mask_realign",
-                 "cast_two_pass", "bwd_ds_lab", "cast_u", "quant_block_wg", "cast_wait_us", "cbal", "cbal_delta", "decode_ks", "sync_chunks", "sync_chunked_calls", "mirror_cache_hits")
+                 "cast_two_pass", "bwd_ds_lab", "cast_u", "quant_block_wg", "cast_wait_us", "cbal", "cbal_delta", "decode_ks", "sync_chunks", "sync_chunked_calls", "mirror_cache_hits", "no_bwd_mask")
 
 
 def get_option(name: str) -> str:
@@ -321,10 +321,13 @@ def gpu_latency() -> float:
 
 
 def attention_backward(dout, q, k, v, o32, lse, *, scale: float, causal: bool = False, grads_in_input_type: bool = True,
-                       intermediate_dtype=None, keep_fp32: bool = False):
+                       intermediate_dtype=None, keep_fp32: bool = False, mask: Optional[torch.Tensor] = None, window=None):
     """dQ, dK, dV of the SDPA in-stream (umfa_attention_backward_stream): contiguous BHSD device tensors, O fp32 and LSE
     from the forward; asynchronous on torch's current stream.  Gradients come back in q.dtype straight from the kernels
-    when the 16-bit MFMA backward serves the call, else fp32 tensors cast afterwards (same values the blocking ABI gives)."""
+    when the 16-bit MFMA backward serves the call, else fp32 tensors cast afterwards (same values the blocking ABI gives).
+
+    mask / window: the forward call's mask (any strides, as attention_forward takes it) or sliding window (left, right)
+    -- umfa_attention_backward_masked_stream; head_dim <= 256.  With neither, the unmasked call."""
     B, H, Sq, D = q.shape
     Skv = k.shape[2]
     for t in (dout, q, k, v, o32, lse):
@@ -335,13 +338,26 @@ def attention_backward(dout, q, k, v, o32, lse, *, scale: float, causal: bool = 
     dvec = torch.empty((B * H * Sq,), dtype=torch.float32, device=q.device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
 
+    if window is not None:
+        if mask is not None:
+            raise ValueError("window and mask are exclusive")
+        margs = (None, _i64((int(window[0]), int(window[1]))), None, 0, 3, MFA_MASK_SCALAR_BYTE)
+    elif mask is not None:
+        margs = _mask_args(mask)
+    else:
+        margs = None
+
     def call(gdt, typed):
         dq = torch.empty((B, H, Sq, D), dtype=gdt, device=q.device)
         dk = torch.empty((B, H, Skv, D), dtype=gdt, device=q.device)
         dv = torch.empty_like(dk)
-        rc = _lib.umfa_attention_backward_stream(
-            context(), stream, *(ctypes.c_void_p(t.data_ptr()) for t in (dout, q, k, v, o32, lse, dq, dk, dv, dvec)),
-            B, Sq, Skv, H, D, float(scale), bool(causal), _PREC[q.dtype], inter, typed, o_typed)
+        ptrs = (ctypes.c_void_p(t.data_ptr()) for t in (dout, q, k, v, o32, lse, dq, dk, dv, dvec))
+        if margs is None:
+            rc = _lib.umfa_attention_backward_stream(context(), stream, *ptrs, B, Sq, Skv, H, D, float(scale), bool(causal),
+                                                     _PREC[q.dtype], inter, typed, o_typed)
+        else:
+            rc = _lib.umfa_attention_backward_masked_stream(context(), stream, *ptrs, B, Sq, Skv, H, D, float(scale), bool(causal),
+                                                            _PREC[q.dtype], inter, typed, o_typed, *margs)
         return rc, dq, dk, dv
 
     if grads_in_input_type and not keep_fp32 and q.dtype != torch.float32:

@@ -84,25 +84,32 @@ def _dev_bufs(*tensors):
 
 
 class _FlashAttentionFn(torch.autograd.Function):
-    """MetalFlashAttentionFn (:2672-2870): fp32 O + LSE saved, backward through mfa_attention_backward."""
+    """MetalFlashAttentionFn (:2672-2870): fp32 O + LSE saved, backward through mfa_attention_backward.
+    mask / window: the forward's attention mask (saved as it came in: no copy, autograd's version counter guards in-place
+    edits) or sliding window (left, right); the backward reads the same (umfa_attention_backward_masked_stream).  The
+    reference's backward takes no mask (:1798-1803); the mask itself gets no gradient here."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float):
+    def forward(ctx, q, k, v, causal: bool, scale: float, mask=None, window=None):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         # O in the operand type from the kernel's epilogue; the SAME tensor serves D = rowsum(dO o O) in the backward
         # (the reference keeps a separate fp32 O for that, :2672-2870: twice the activation, one more cast)
-        out, lse = ops.attention_forward(q, k, v, scale=scale, causal=causal, out_dtype=q.dtype, return_lse=True)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.causal, ctx.scale = causal, scale
+        out, lse = ops.attention_forward(q, k, v, scale=scale, causal=causal, mask=mask, window=window, out_dtype=q.dtype,
+                                         return_lse=True)
+        if mask is not None:
+            ctx.save_for_backward(q, k, v, out, lse, mask)
+        else:
+            ctx.save_for_backward(q, k, v, out, lse)
+        ctx.causal, ctx.scale, ctx.window = causal, scale, window
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, o32, lse = ctx.saved_tensors
+        q, k, v, o32, lse, *m = ctx.saved_tensors
         # in-stream (no host synchronisation), gradients in the operand type straight from the kernels' epilogues
         dq, dk, dv = ops.attention_backward(dout.to(q.dtype).contiguous(), q, k, v, o32, lse, scale=float(ctx.scale),
-                                            causal=bool(ctx.causal))
-        return dq, dk, dv, None, None
+                                            causal=bool(ctx.causal), mask=m[0] if m else None, window=ctx.window)
+        return dq, dk, dv, None, None, None, None
 
 
 class _GqaFlashAttentionFn(torch.autograd.Function):
@@ -182,6 +189,44 @@ class _QuantizedFlashAttentionFn(torch.autograd.Function):
             for b in bufs:
                 b.close()
         return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None, None
+
+
+# Masked training goes to the kernels where they are measured faster end to end (forward + backward) than torch's own SDPA with the
+# same mask (tools/bench_masked_backward.py, profiles/masked_bwd/bench.jsonl): bf16 / fp16 at head_dim 64 and 128.  Torch keeps the
+# rest: fp32 operands and head dims other than 64 / 128 / 256 (the fp32-exact engine: 3-6x slower than torch there), head_dim 256
+# (0.84 vs 0.74 ms at B1 H8 S2048 key padding), a learnable mask (its gradient is not built here) and the A/B option no_bwd_mask.
+MASKED_TRAINING_HEAD_DIMS = (64, 128)
+
+
+def masked_training_served(mask, q) -> bool:
+    return (not mask.requires_grad and q.dtype in (torch.float16, torch.bfloat16) and q.size(-1) in MASKED_TRAINING_HEAD_DIMS
+            and ops.get_option("no_bwd_mask") == "0")
+
+
+def sliding_window_attention(query, key, value, window, causal: bool = False, scale: Optional[float] = None):
+    """Attention in which key j is visible to query i iff i - left <= j <= i + right, window = (left, right) -- torch's SDPA has
+    no window argument.  BHSD device tensors of one dtype (fp32 / fp16 / bf16), head_dim <= 256 when a gradient is needed;
+    causal=True keeps only the look-back part.  Differentiable w.r.t. query, key and value; no mask tensor is built: tiles
+    outside the band are never touched, forward or backward, so the cost follows the band."""
+    left, right = int(window[0]), int(window[1])
+    if left < 0 or right < 0:
+        raise ValueError("window sizes must be >= 0")
+    q, k, v = query, key, value
+    if (q.dim() != 4 or k.dim() != 4 or v.dim() != 4 or not (q.is_cuda and k.is_cuda and v.is_cuda) or q.dtype not in _SUPPORTED
+            or k.dtype != q.dtype or v.dtype != q.dtype or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[1] != k.shape[1]
+            or q.shape[3] != k.shape[3] or q.shape[3] == 0):
+        raise ValueError("sliding_window_attention: BHSD device tensors of one dtype (fp32 / fp16 / bf16) with matching shapes")
+    sm_scale = float(scale) if scale is not None else float(q.size(-1)) ** -0.5
+    _bump("total")
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        if q.size(-1) > 256:
+            raise ValueError("sliding_window_attention: no backward above head_dim 256")
+        _bump("fp32_autograd")
+        return _FlashAttentionFn.apply(q, k, v, bool(causal), sm_scale, None, (left, right))
+    _bump("fp32_instream")
+    if q.stride(-1) != 1 or k.stride(-1) != 1 or v.stride(-1) != 1:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    return ops.attention_forward(q, k, v, scale=sm_scale, causal=bool(causal), window=(left, right), out_dtype=q.dtype)
 
 
 def _gqa_zero_copy(q, k, v, attn_mask, dropout_p, is_causal, scale):
@@ -319,10 +364,10 @@ def scaled_dot_product_attention(query, key, value, attn_mask: Optional[torch.Te
         out = _QuantizedFlashAttentionFn.apply(q, k, v, bool(is_causal), sm_scale, _quant_precision, _quant_mode, mask)
         return out.to(query.dtype)
     if q.requires_grad or k.requires_grad or v.requires_grad:
-        if mask is not None:
-            return fallback()  # dense backward takes no mask (:1798-1803)
+        if mask is not None and (is_causal or not masked_training_served(mask, q)):  # (causal + mask: torch's error)
+            return fallback()  # (the reference's backward takes no mask at all, :1798-1803)
         _bump("fp32_autograd")
-        return _FlashAttentionFn.apply(q, k, v, bool(is_causal), sm_scale)
+        return _FlashAttentionFn.apply(q, k, v, bool(is_causal), sm_scale, mask)
     # inference: in-stream, zero-copy, output directly in the input dtype (v)
     for t in (q, k, v):
         if t.stride(-1) != 1:
