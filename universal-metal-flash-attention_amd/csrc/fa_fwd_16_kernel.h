@@ -136,6 +136,17 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
 constexpr int fwd16_threads(int KS) { return KS == 4 ? 256 : 256 * KS; }
 constexpr int fwd16_resident(int DP, int BN, int KS) { return KS == 4 ? (DP > 64 ? 1 : 2) : KS * (DP > 128 ? 1 : (BN == 32 ? 3 : 2)); }
 
+// Words of the tile area the epilogue reserves behind the loop (32-bit words from the dynamic LDS base):
+//   FWD16_EPI_RED .. + waves - 1   v_range_check's red[wave] (written, barrier, read by every wave -- no barrier after the reads)
+//   FWD16_EPI_FLAG                 the split-KV ticket / the CBAL pair's flag (tid 0 writes, barrier, every wave reads)
+// The decode form's (KS = 4) key-quarter exchange starts at FWD16_EPI_HDR, behind both: a quarter that publishes its partial O
+// while a slower wave still reads its range-check word must not overwrite that word.
+constexpr int FWD16_EPI_RED = 0;
+constexpr int FWD16_EPI_FLAG = 16;
+constexpr int FWD16_EPI_HDR = 64;  // 256 bytes
+// the decode form's exchange: three publishing quarters x (16 NDB O^T registers + m + l) x 64 lanes, in words
+constexpr int fwd16_decode_exchange_words(int DP) { return 3 * (16 * (DP / 32) + 2) * 64; }
+
 template <typename T, int DP, bool CAUSAL, bool HAS_MASK, typename OUT, bool DMA = false, int BN = 64, int PV16 = 0, int KS = 1, int PIPE = 0, bool CBAL = false>
 __global__ __launch_bounds__(fwd16_threads(KS), fwd16_resident(DP, BN, KS)) void fa_fwd16_kernel(FwdParams p) {
     if constexpr (HAS_MASK) {
@@ -591,8 +602,9 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
 #pragma unroll
         for (int w2 = 0; w2 < NT / 64; ++w2) all |= red[w2];
         all = __builtin_amdgcn_readfirstlane(all);
-        // non-finite, or rows with keys and nothing above 2^-11  (otherwise on: the words stay -- the tile area is not read again, and the
-        // folds below write before they read)
+        // non-finite, or rows with keys and nothing above 2^-11  (otherwise on: the words stay and NO barrier follows these reads -- a
+        // wave may still be here while the others go on, so nothing behind the loop may write the words FWD16_EPI_RED .. + NW - 1: the
+        // ticket / flag word is FWD16_EPI_FLAG, the decode form's exchange starts at FWD16_EPI_HDR)
         if (__builtin_expect((all & 1u) || ((all & 4u) && !(all & 2u)), 0)) {
             unsigned amax = 0;
             const uint32_t d8 = (uint32_t)D / 8u, nch = p.Skv * d8;
@@ -615,7 +627,10 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
             __syncthreads();
             amax = 0;
 #pragma unroll
-            for (int w2 = 0; w2 < NT / 64; ++w2) amax = amax > red[w2] ? amax : red[w2];
+            for (int w2 = 0; w2 < NT / 64; ++w2) {
+                const unsigned rv = red[w2];  // (one read of the volatile word: selecting between two lvalues put amax on the stack)
+                amax = amax > rv ? amax : rv;
+            }
             amax = __builtin_amdgcn_readfirstlane(amax);
             __syncthreads();
             // V all zero (the outputs were right), V with inf / NaN in it (they are what they should be: non-finite), V already where the
@@ -1132,7 +1147,7 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
 
     if constexpr (VCONV && !RESWEEP) {
         if constexpr (NS > 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the ring's youngest requests still land in the tile area)
-        if (const int e2 = v_range_check((volatile uint32_t*)smem)) return (e2 & 0xffff) | (CBAL && cb_role == 2 ? 0x10000 : 0);
+        if (const int e2 = v_range_check((volatile uint32_t*)smem + FWD16_EPI_RED)) return (e2 & 0xffff) | (CBAL && cb_role == 2 ? 0x10000 : 0);
     }
     v_shift_back();
 
@@ -1150,7 +1165,14 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
         // stage_write waited vmcnt(0)) and the loop's last barrier is behind every wave's last tile read.
         constexpr int NREG = 16 * NDB + 2;
         constexpr int NOTH = KS == 4 ? 3 : 1;  // publishing parts per row-wave
-        float* const ex0 = (float*)smem + (KS == 4 ? 0 : rw * (NREG * 64)) + lane;  // (KS = 4: areas 0 .. 2 for quarters 1 .. 3)
+        // KS = 4: areas 0 .. 2 for quarters 1 .. 3, behind the reserved header (no barrier follows v_range_check's reads of red[], and
+        // NS = 2 compiles the one below out: quarter 1 would otherwise overwrite words 0 .. 3 while another wave still reads them).
+        // KS = 2: from word 0 -- its NS = 4 barrier below runs first.
+        constexpr int EX4 = FWD16_EPI_HDR;  // (KS = 4: first word of area 0)
+        static_assert(KS != 4 || (FWD16_EPI_RED + NW <= FWD16_EPI_FLAG && FWD16_EPI_FLAG < FWD16_EPI_HDR && EX4 >= FWD16_EPI_HDR &&
+                                  fwd16_decode_exchange_words(DP) == 3 * NREG * 64 && (EX4 + 3 * NREG * 64) * 4 <= 2 * NS * TILE_BYTES),
+                      "decode form: the exchange areas [HDR, HDR + 3 NREG 64) lie behind the reserved words and inside the tile area");
+        float* const ex0 = (float*)smem + (KS == 4 ? EX4 : rw * (NREG * 64)) + lane;
         if constexpr (NS > 2) {  // the ring's youngest requests (tiles past the end) are still on their way into the tile area
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -1189,8 +1211,8 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
         if (cb_role == 1) {
             // part A: fold the pair's part B in (it was published tiles ago: B's share of the long q-block is the shorter one).  The wait is
             // bounded all the same -- two seconds, then the rows come out NaN rather than the queue hanging
-            // (the tile area is free: every LDS-DMA write has landed, every wave is behind the loop's last barrier; word 16: the range check's four words may still be read)
-            volatile uint32_t& flag_s = *((volatile uint32_t*)smem + 16);
+            // (the tile area is free: every LDS-DMA write has landed, every wave is behind the loop's last barrier; word FWD16_EPI_FLAG: the range check's four words may still be read)
+            volatile uint32_t& flag_s = *((volatile uint32_t*)smem + FWD16_EPI_FLAG);
             if (tid == 0) {
                 const uint64_t t_in = __builtin_amdgcn_s_memrealtime();
                 uint32_t f = cb_early;
@@ -1238,14 +1260,14 @@ __device__ __forceinline__ int fa_fwd16_body(PRM& p, const int vexp_in, const in
         constexpr int NCHK = 4 * NDB + 1;
         // (fwd_16_split_plan sizes the buffer: 16 NDB + 4 words per lane, wave and part)
         // every static __shared__ object would shift the dynamic LDS base (Guideline 17): reuse the tile area
-        volatile uint32_t& ticket_s = *((volatile uint32_t*)smem + 16);
+        volatile uint32_t& ticket_s = *((volatile uint32_t*)smem + FWD16_EPI_FLAG);  // (the range check's words may still be read: not those)
         const uint32_t sidx = item - p.n_full;
         const size_t item_bytes = (size_t)nparts * 4 * (size_t)(NCHK * 1024);
         const auto prs = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.part_buf + (size_t)sidx * item_bytes), 0, (int)item_bytes, 0x00020000);
         auto slot = [&](uint32_t part_, int chunk) -> int { return (int)(((part_ * 4 + (uint32_t)wave) * NCHK + (uint32_t)chunk) * 1024u) + lane * 16; };
         constexpr int SC1 = 16;  // cache policy bit of the buffer builtins: system-coherent level 1 = write-through / read-around the XCD's L2
         typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-        if constexpr (KS == 4) __syncthreads();  // (the exchange areas above sit in the tile area the ticket word below is in)
+        if constexpr (KS == 4) __syncthreads();  // (wave 0's reads of the exchange areas are behind every wave before the ticket word below is written)
         const bool wave_rows = wave_q0 < p.Sq && lead;  // (wave-uniform)
         if (wave_rows) {
 #pragma unroll

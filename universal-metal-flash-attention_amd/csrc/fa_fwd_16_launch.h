@@ -23,7 +23,8 @@ static inline hipError_t launch_dma(const FwdParams& pin, hipStream_t stream) {
     const size_t lds = (KS == 2 ? 8 : 4) * BN * DP * 2;
 #endif
     static_assert(KS != 2 || 8 * BN * DP * 2 >= 4 * (16 * (DP / 32) + 2) * 256, "exchange area");
-    static_assert(KS != 4 || 4 * BN * DP * 2 >= 3 * (16 * (DP / 32) + 2) * 256 + 256, "exchange area (decode form)");
+    // decode form: the reserved header (range-check words, ticket / flag word: FWD16_EPI_HDR words), then the three key quarters' exchange
+    static_assert(KS != 4 || 4 * BN * DP * 2 >= 4 * (FWD16_EPI_HDR + fwd16_decode_exchange_words(DP)), "exchange area (decode form)");
     auto kfn = fa_fwd16_kernel<T, DP, CAUSAL, HAS_MASK, OUT, DMA, BN, PV16, KS, PIPE, CBAL>;
     if (hipError_t e = ensure_dynamic_lds((const void*)kfn, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(fwd16_threads(KS)), lds, stream, p);
