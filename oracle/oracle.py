@@ -348,3 +348,87 @@ def quantized_forward_fp8pv(q, k, v, rows=None, scale=None, causal=False, p_fp8:
     if p_fp8:
         p = round_e4m3(p)
     return (np.einsum("bhij,bhjd->bhid", p, vf) / p.sum(-1, keepdims=True)).astype(np.float32)
+
+
+def _slab_idx(idx, b, h, n):
+    """index set of one (batch, head) slab: None = all n, a 1-D array shared by every slab, or [B, H, R] per slab"""
+    if idx is None:
+        return np.arange(n)
+    idx = np.asarray(idx, np.int64)
+    return idx if idx.ndim == 1 else idx[b, h]
+
+
+def flash_backward_format_floor(dout, q, k, v, out, lse, kind: str, *, scale, causal=False, term=None, kv_group=1,
+                                rows=None, keys=None, budget=1 << 22):
+    """fp64 backward of the SDPA on the O and LSE the kernels were handed, twice: `exact`, and `floor` -- an IDEAL 16-bit
+    backward that rounds P once to `kind` before dV = P^T dO and dS once before dK = scale dS^T Q and dQ = scale dS K (the two
+    roundings fa_bwd_16.hip makes), everything else fp64.  floor - exact is the part of a 16-bit backward's error the
+    operand format fixes.
+
+    q, dout, out [B, H, Sq, D]; k, v [B, H / kv_group, Skv, D] (bf16 as uint16 bits, or any float type); lse [B, H, Sq]
+    (natural log, any shape of B H Sq elements); term: additive fp64 mask broadcastable to [B, H, Sq, Skv], -inf = hidden.
+    causal is top-left aligned (key j <= row i).  A row that sees nothing gets P = 0.  rows: the dQ rows, keys: the dK / dV
+    keys (1-D, or [B, H, R] / [B, Hkv, K] per slab; None = all): a dQ row needs its row and every key, a key row every query.
+    Grouped heads: dK, dV of a K / V head are summed over its kv_group query heads in fp64.
+
+    Returns {"exact": (dq, dk, dv), "floor": (dq, dk, dv), "abs": (dq, dk, dv), "dead": (rows_seeing_nothing [B,H,R] bool,
+    keys_nobody_sees [B,Hkv,K] bool), "ds_max": max|dS|}.  "abs" is the same sums over magnitudes (|P| (|dO| |V| + |dO o O|)
+    for dS): the scale of each element's rounding errors, which bounds an element whose exact value cancels to (near) zero."""
+    B, H, Sq, D = q.shape
+    Hkv, Skv = k.shape[1], k.shape[2]
+    assert H == Hkv * kv_group
+    f64 = lambda a: to_f32(np.asarray(a)).astype(np.float64) if np.asarray(a).dtype == np.uint16 else np.asarray(a, np.float64)  # noqa: E731
+    Q, K, V, dO, O = (f64(a) for a in (q, k, v, dout, out))
+    L = np.asarray(lse, np.float64).reshape(B, H, Sq)
+    T = None if term is None else np.broadcast_to(np.asarray(term, np.float64), (B, H, Sq, Skv))
+    R = len(_slab_idx(rows, 0, 0, Sq))
+    Kn = len(_slab_idx(keys, 0, 0, Skv))
+    res = {n: [np.zeros((B, H, R, D)), np.zeros((B, Hkv, Kn, D)), np.zeros((B, Hkv, Kn, D))] for n in ("exact", "floor", "abs")}
+    dead_r = np.zeros((B, H, R), bool)
+    seen_k = np.zeros((B, Hkv, Kn), bool)
+    ds_max = 0.0
+
+    def block(b, h, ri, kj):
+        """P, dS, |dS| bound of rows ri x keys kj of slab (b, h)"""
+        kh = h // kv_group
+        s = (Q[b, h, ri] @ K[b, kh, kj].T) * scale
+        if T is not None:
+            s = s + T[b, h][np.ix_(ri, kj)]
+        if causal:
+            s = np.where(kj[None, :] <= ri[:, None], s, -np.inf)
+        lr = L[b, h, ri][:, None]
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = np.where(np.isfinite(s) & np.isfinite(lr), np.exp(s - np.where(np.isfinite(lr), lr, 0.0)), 0.0)
+        dvec = (dO[b, h, ri] * O[b, h, ri]).sum(-1)[:, None]
+        ds = p * (dO[b, h, ri] @ V[b, kh, kj].T - dvec)
+        ds_abs = p * (np.abs(dO[b, h, ri]) @ np.abs(V[b, kh, kj]).T + np.abs(dO[b, h, ri] * O[b, h, ri]).sum(-1)[:, None])
+        return p, ds, ds_abs
+
+    for b in range(B):
+        for h in range(H):
+            kh = h // kv_group
+            ri = _slab_idx(rows, b, h, Sq)
+            step = max(1, budget // max(Skv, 1))  # (score-sized temporaries of at most `budget` elements)
+            for c0 in range(0, R, step):  # dQ rows: all keys
+                rc = ri[c0:c0 + step]
+                sl = slice(c0, c0 + len(rc))
+                p, ds, ds_abs = block(b, h, rc, np.arange(Skv))
+                ds_max = max(ds_max, float(np.abs(ds).max(initial=0.0)))
+                res["exact"][0][b, h, sl] = scale * ds @ K[b, kh]
+                res["floor"][0][b, h, sl] = scale * round_to(ds, kind) @ K[b, kh]
+                res["abs"][0][b, h, sl] = scale * ds_abs @ np.abs(K[b, kh])
+                dead_r[b, h, sl] = ~(p > 0).any(-1)
+            kj = _slab_idx(keys, b, kh, Skv)
+            step = max(1, budget // max(Kn, 1))
+            for c0 in range(0, Sq, step):  # dK / dV keys: all queries
+                rc = np.arange(c0, min(Sq, c0 + step))
+                p, ds, ds_abs = block(b, h, rc, kj)
+                ds_max = max(ds_max, float(np.abs(ds).max(initial=0.0)))
+                for n, pp, dd in (("exact", p, ds), ("floor", round_to(p, kind), round_to(ds, kind)), ("abs", p, ds_abs)):
+                    res[n][2][b, kh] += pp.T @ (dO[b, h, rc] if n != "abs" else np.abs(dO[b, h, rc]))
+                    res[n][1][b, kh] += scale * dd.T @ (Q[b, h, rc] if n != "abs" else np.abs(Q[b, h, rc]))
+                seen_k[b, kh] |= (p > 0).any(0)
+    out_ = {n: tuple(res[n]) for n in res}
+    out_["dead"] = (dead_r, ~seen_k)
+    out_["ds_max"] = ds_max
+    return out_

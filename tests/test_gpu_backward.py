@@ -22,6 +22,14 @@ def _oracle():
     return oracle
 
 
+def _check_floor(ctx, grads, inputs, dt, causal, ceiling, tag):
+    """the 16-bit backward's gradients against the format floor on the same O and LSE (tests/tolerances.py check_backward)"""
+    import tolerances
+    do, q, k, v, o, lse = inputs
+    fl = _oracle().flash_backward_format_floor(do, q, k, v, o, lse, dt, scale=q.shape[-1] ** -0.5, causal=causal)
+    tolerances.check_backward(grads, fl, dt, tag=tag, kernel=ctx.last_kernel, ceiling=ceiling)
+
+
 @pytest.mark.parametrize("tag", ["dense", "causal"])
 def test_backward_golden_fp32(ctx, golden_dir, tag):
     import umfa
@@ -103,6 +111,7 @@ def test_backward_mfma16_vs_oracle(ctx, shape, dt, causal):
         cos = float((got * ref).sum() / np.sqrt((got ** 2).sum() * (ref ** 2).sum()))
         assert rel < tol and cos > 0.9999, (name, rel, cos)
     assert np.abs(dvec.reshape(rd.shape) - rd).max() < 1e-3
+    _check_floor(ctx, (dq, dk, dv), (do, q, k, v, o, lse), dt, causal, {"bf16": 2e-2, "fp16": 4e-3}, f"mfma16 {shape} causal={causal}")
     # intermediate_precision = fp32 keeps the exact kernel available for the same operands
     dq2, dk2, dv2, _ = umfa.attention_backward(ctx, do, q, k, v, o, lse.ravel(), causal=causal, input_precision=dt,
                                                intermediate_precision="fp32")
@@ -321,6 +330,7 @@ def test_backward_both_dq_kernels_head_dim_128(ctx, which, causal, umfa_opts):
         for got, ref, name in [(dq, rdq, "dq"), (dk, rdk, "dk"), (dv, rdv, "dv")]:
             rel = np.abs(got - ref).max() / np.abs(ref).max()
             assert np.isfinite(got).all() and rel < 2e-2, (which, causal, shape, name, rel)
+        _check_floor(ctx, (dq, dk, dv), (do, q, k, v, o, lse), "bf16", causal, {"bf16": 2e-2}, f"bwd_dq={which} {shape} causal={causal}")
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

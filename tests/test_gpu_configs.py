@@ -143,6 +143,9 @@ def test_config3_flux_fwd_bwd_bf16():
                                                    o_s, l_s.ravel(), input_precision="bf16")
     for g, r in ((gdq, rdq), (gdk, rdk), (gdv, rdv)):
         assert np.abs(g - r).max() < BWD16_TOL * np.abs(r).max()  # bf16 MFMA backward (P, dS rounded to bf16): measured 4e-3
+    from tolerances import check_backward
+    fl = orc.flash_backward_format_floor(*(bits(t[:, :1, :S2].contiguous()) for t in (do, q, k, v)), o_s, l_s, "bf16", scale=D ** -0.5)
+    check_backward((gdq, gdk, gdv), fl, "bf16", tag="cfg3_flux_bwd_S256", kernel="fa_bwd16<bf16,128>", ceiling={"bf16": BWD16_TOL})
     # ... and AT config size: a gradient row depends on its own row of Q / dO / O / LSE and every key (dQ), a gradient key row on its own
     # K / V row and every query row (dK, dV) -- the oracle is handed the GPU forward's fp32 O and LSE (what the kernels were handed), so a
     # row subset of the oracle's backward IS the full-size gradient on those rows
@@ -160,6 +163,11 @@ def test_config3_flux_fwd_bwd_bf16():
         for name, g, r in (("dq", dq[:, h:h + 1][:, :, rows], rdq_r), ("dk", dk[:, h:h + 1][:, :, keys], rdk_k), ("dv", dv[:, h:h + 1][:, :, keys], rdv_k)):
             e = float(np.abs(g.cpu().numpy() - r).max() / np.abs(r).max())
             assert e < BWD16_TOL, (name, h, e)
+    # the same heads, rows and keys against the gradient format floor (fp64 on the GPU forward's O and LSE, P and dS rounded once)
+    fl = orc.flash_backward_format_floor(*(bits(t[:, heads]) for t in (do, q, k, v)), o_np[:, heads], lse_np[:, heads], "bf16",
+                                         scale=D ** -0.5, rows=rows, keys=keys)
+    got = [g[:, heads][:, :, torch.as_tensor(idx, device=g.device)].cpu().numpy() for g, idx in ((dq, rows), (dk, keys), (dv, keys))]
+    check_backward(got, fl, "bf16", tag="cfg3_flux_bwd_subset", kernel="fa_bwd16<bf16,128>", ceiling={"bf16": BWD16_TOL})
 
 
 def test_config4_int8_blockwise_S8192_H16_D128():

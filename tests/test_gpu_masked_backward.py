@@ -49,11 +49,11 @@ def ref_grads(q, k, v, dout, term, causal, scale):
     return qd.grad, kd.grad, vd.grad
 
 
-def run(ut, q, k, v, dout, scale, causal, mask=None, window=None):
+def run(ut, q, k, v, dout, scale, causal, mask=None, window=None, with_fwd=False):
     out, lse = ut.attention_forward(q, k, v, scale=scale, causal=causal, mask=mask, window=window, out_dtype=q.dtype, return_lse=True)
     g = ut.attention_backward(dout, q, k, v, out, lse, scale=scale, causal=causal, mask=mask, window=window)
     torch.cuda.synchronize()
-    return g
+    return (g, out, lse) if with_fwd else g
 
 
 def rel_err(g, r):
@@ -128,12 +128,12 @@ def test_masked_backward_matches_fp64(ut, dt, D, kind, shape):
     scale = D ** -0.5
     if kind == "window":
         win = (int(torch.randint(0, 80, (1,), generator=gen)), int(torch.randint(0, 80, (1,), generator=gen)))
-        g = run(ut, q, k, v, dout, scale, causal, window=win)
+        g, out, lse = run(ut, q, k, v, dout, scale, causal, window=win, with_fwd=True)
         term = window_term(Sq, Skv, *win).expand(B, H, Sq, Skv)
         want = "window"
     else:
         m = make_mask(kind, shape, B, H, Sq, Skv, gen)
-        g = run(ut, q, k, v, dout, scale, causal, mask=m)
+        g, out, lse = run(ut, q, k, v, dout, scale, causal, mask=m, with_fwd=True)
         term = term_of(m, (B, H, Sq, Skv))
         want = "mask"
     kern = ut.last_kernel()
@@ -145,6 +145,15 @@ def test_masked_backward_matches_fp64(ut, dt, D, kind, shape):
     for name, gi, ri in zip("qkv", g, r):
         assert torch.isfinite(gi).all(), name
         assert rel_err(gi, ri) <= TOL[dt], (name, rel_err(gi, ri))
+    if kern.startswith("fa_bwd16<"):  # and the gradient format floor on the O (operand type) and LSE the kernel was handed
+        import tolerances
+        from oracle import oracle
+        kd = "bf16" if dt == torch.bfloat16 else "fp16"
+        npy = lambda t: t.detach().float().cpu().numpy()  # noqa: E731
+        fl = oracle.flash_backward_format_floor(npy(dout), npy(q), npy(k), npy(v), npy(out), npy(lse), kd, scale=scale, causal=causal,
+                                                term=term.numpy())
+        tolerances.check_backward([npy(gi) for gi in g], fl, kd, tag=f"masked {kind} {shape} d{D}", kernel=kern, grad_dt=kd,
+                                  ceiling={kd: TOL[dt]})
 
 
 def test_bf16_d128_moderate_size_within_bwd16_tol(ut):

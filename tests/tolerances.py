@@ -139,3 +139,107 @@ def check_forward(o, ref, dt, kernel: str, tag: str = "", scale_max: float = 1.0
         if np.asarray(ref)[:, :, :MAX_FLOOR_ROWS].size >= min_elems_for_rms:
             assert krms <= mrms * scale_max * frms, (tag, kernel, regime, "rms vs format floor", krms, frms, mrms * scale_max)
     return mx, rms
+
+
+# ------------------------------------------------------------------------------------------------------ 16-bit backward
+# Gradient bounds of fa_bwd16 / fa_bwd16_mask (DESIGN.md §3.2), the same two kinds as the forward's.  Metric per gradient
+# (dQ, dK, dV): errors() against the fp64 backward run on the O and LSE the kernel was handed (oracle.flash_backward_format_floor
+# "exact").  The floor is the ideal 16-bit backward: P rounded once before dV = P^T dO, dS once before dK and dQ.
+# (multiple of the floor's max, multiple of the floor's rms).  The kernels round the same P and dS the floor does (their fp32 values
+# agree with fp64 to ~1e-6, so nearly every rounding lands on the same bits): measured worst 1.014 / 1.001 over 179 GPU cases
+# (profiles/bwd_floor/parity_record.jsonl).  A kernel 15 % worse everywhere fails the rms bound.
+BWD_FLOOR_MULT = (1.10, 1.05)
+# fixed ceilings of the max error (the bounds the suite held the 16-bit backward to before the floor: fuzz / masked tests)
+BWD_CEILING = {"bf16": 3e-2, "fp16": 8e-3}
+# a gradient whose exact values cancel to below this fraction of the magnitude of their terms has no usable ratio (dQ at
+# Skv = 1: dP - D is rounding noise): it is held element by element to the absolute bound below instead
+BWD_NEAR_ZERO = 1e-3
+BWD_EPS = 2.0 ** -20  # fp32 sums of a few thousand terms: an absolute allowance, relative to max|exact|, beside the floor
+
+
+def sample_rows(n: int, B: int, H: int, seed: int, block: int = 128, interior: int = 8) -> np.ndarray:
+    """[B, H, R] sorted row (or key) indices per (batch, head) slab: the first and last index of every `block`-sized block
+    (the ragged tail's last is n - 1), so every workgroup the grids schedule is looked at, plus `interior` seeded indices
+    per slab (distinct between slabs) from the rest."""
+    ends = np.unique(np.concatenate([np.arange(0, n, block), np.minimum(np.arange(block - 1, n + block - 1, block), n - 1)]))
+    rest = np.setdiff1d(np.arange(n), ends)
+    m = min(interior, rest.size)
+    rng = np.random.default_rng(seed)
+    out = np.empty((B, H, ends.size + m), np.int64)
+    for b in range(B):
+        for h in range(H):
+            out[b, h] = np.sort(np.concatenate([ends, rng.choice(rest, m, replace=False)]))
+    return out
+
+
+def gather_rows(x, idx):
+    """x [B, H, S, D] at per-slab indices idx [B, H, R] (or 1-D, or None = all) -> [B, H, R, D]"""
+    x = np.asarray(x)
+    if idx is None:
+        return x
+    idx = np.asarray(idx, np.int64)
+    if idx.ndim == 1:
+        return x[:, :, idx]
+    return np.take_along_axis(x, idx[..., None], axis=2)
+
+
+def check_backward(got, fl, dt, tag: str = "", kernel: str = "", grad_dt=None, ceiling=None, scale_max: float = 1.0,
+                   min_elems_for_rms: int = 4096):
+    """Assert the 16-bit backward's gradient bounds.
+
+    got = (dq, dk, dv) on the elements fl describes (gather_rows for a subset); fl = oracle.flash_backward_format_floor(...).
+    dt: the operand type (the format of P and dS).  grad_dt: the type the gradients were stored in when not fp32 (adds one
+    rounding of each gradient: the floor is rounded the same way, and the max bound gains OUT_HALF_ULP).  ceiling: the
+    fixed max bound (default BWD_CEILING).  scale_max loosens the ceiling for deliberately hostile inputs (stated at the
+    call site); the floor-relative bounds are never loosened.  Per gradient:
+      - finite; exact zeros where the floor's are (rows that see nothing, keys nobody sees);
+      - element by element |g - exact| <= ulp(1) x (the same sum over magnitudes), the bound of any one-rounding kernel;
+      - unless the gradient cancels to near zero (BWD_NEAR_ZERO): max <= ceiling, and max / rms <= BWD_FLOOR_MULT x the floor's
+        on the same elements (max widened by SMALL_SAMPLE_SLACK below SMALL_SAMPLE elements, rms from min_elems_for_rms)."""
+    name = _name(dt)
+    gname = _name(grad_dt) if grad_dt is not None and _name(grad_dt) in OUT_HALF_ULP else None
+    h = OUT_HALF_ULP[gname] if gname else 0.0
+    ceil = (ceiling or BWD_CEILING)[name] * scale_max
+    mmax0, mrms = BWD_FLOOR_MULT
+    dead_r, dead_k = fl["dead"]
+    out = {}
+    for i, g_name in enumerate(("dq", "dk", "dv")):
+        g = np.asarray(got[i], np.float64)
+        ex, floor, ab = fl["exact"][i], fl["floor"][i], fl["abs"][i]
+        assert g.shape == ex.shape, (tag, g_name, g.shape, ex.shape)
+        assert np.isfinite(g).all(), (tag, kernel, g_name, "non-finite gradient")
+        dead = dead_r if i == 0 else dead_k
+        if dead.any():
+            nz = np.abs(g[dead]).max()
+            assert nz == 0.0, (tag, kernel, g_name, "not exactly zero where no score is seen", nz, int(dead.sum()))
+        if gname:
+            floor = round_to_kind(floor, gname)
+        err = np.abs(g - ex)
+        amax = max(float(np.abs(ex).max(initial=0.0)), 1e-30)
+        lim = ULP_AT_ONE[name] * ab + h * (np.abs(ex) + ULP_AT_ONE[name] * ab) + BWD_EPS * amax
+        worst = np.unravel_index(int(np.argmax(err - lim)), err.shape) if err.size else ()
+        n = int(ex.size)
+        near_zero = amax <= BWD_NEAR_ZERO * float(ab.max(initial=0.0))
+        rec = dict(dtype=name, kernel=kernel, grad=g_name, out=gname or "fp32", n=n, near_zero=bool(near_zero),
+                   abs_excess=float((err - lim).max(initial=-1.0)))
+        if not near_zero:
+            kmax, krms = errors(g, ex)
+            fmax, frms = errors(floor, ex)
+            mmax = mmax0 * (SMALL_SAMPLE_SLACK if n < SMALL_SAMPLE else 1.0)
+            rec.update(max=kmax, rms=krms, floor_max=fmax, floor_rms=frms, ratio_max=kmax / max(fmax, 1e-30),
+                       ratio_rms=krms / max(frms, 1e-30), ceiling_max=ceil, mult_max=mmax, mult_rms=mrms)
+        record(tag or kernel, **rec)
+        assert (err <= lim).all(), (tag, kernel, g_name, "element bound", "at", tuple(int(x) for x in worst), float(err[worst]),
+                                    float(lim[worst]))
+        if not near_zero:
+            assert kmax <= ceil, (tag, kernel, g_name, "format ceiling, max", kmax, ceil)
+            assert kmax <= mmax * fmax + h + BWD_EPS, (tag, kernel, g_name, "max vs format floor", kmax, fmax, mmax)
+            if n >= min_elems_for_rms:
+                assert krms <= mrms * frms + BWD_EPS, (tag, kernel, g_name, "rms vs format floor", krms, frms, mrms)
+        out[g_name] = rec
+    return out
+
+
+def round_to_kind(x, kind: str):
+    from oracle import oracle
+    return oracle.round_to(np.asarray(x, np.float64), kind)
