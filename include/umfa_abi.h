@@ -385,6 +385,41 @@ mfa_error_t umfa_attention_backward_masked_stream(mfa_context_t context, void* s
                                                   uint32_t mask_ndim, mfa_mask_type_t mask_type,
                                                   mfa_mask_scalar_t mask_scalar_type);
 
+/* MI355X extra: attention dropout (torch's dropout_p).  The keep mask is a pure function of (query row i, key j, b * H + h) and
+ * rng_state, a DEVICE int64[2] = {seed, offset} the kernels read when they run (so a captured graph whose rng_state is rewritten between
+ * replays draws a new mask each time): w = Philox4x32-10(ctr = (j >> 2, i, b*H + h, lo32(offset)), key = (lo32(seed), hi32(seed)))[j & 3],
+ * t = min(round(p 2^32), 2^32 - 1), keep = (w >= t), scale s = 2^32 / (2^32 - t).
+ * The forward: the arguments of umfa_attention_forward_stream without the mask group.  O = s * sum_j keep_ij P_ij V_j with P the
+ * softmax over the visible keys (causal first); lse receives the UNDROPPED log-sum-exp (may be NULL).  Scope: fp16 / bf16 operands,
+ * head_dim 64 / 128, 16-bit intermediates, K / V rows contiguous (strides {*, *, head_dim, 1}), 16-byte aligned, out fp32 or the operand
+ * type, 0 < dropout_p < 1, rng_state non-NULL; anything else is MFA_ERROR_INVALID_ARGS (never a silent fall-back).
+ * In-stream, never synchronises; valid under stream capture after a warm-up call (bf16 takes a V image from the stream's scratch). */
+mfa_error_t umfa_attention_forward_dropout_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, const void* k,
+    const int64_t* k_strides, const void* v, const int64_t* v_strides, void* out, int32_t out_precision, float* lse,
+    uint32_t batch_size, uint32_t seq_len_q, uint32_t seq_len_kv, uint32_t num_heads, uint16_t head_dim,
+    float softmax_scale, bool causal, int32_t input_precision, int32_t intermediate_precision, float dropout_p,
+    const int64_t* rng_state);
+
+/* MI355X extra: the backward of umfa_attention_forward_dropout_stream: the arguments of umfa_attention_backward_stream plus the
+ * forward's dropout_p and rng_state (the same mask, bit for bit).  out is the dropped O the forward returned, softmax_lse its LSE;
+ * dense BHSD operands.  Scope as the forward (fp16 / bf16, head_dim 64 / 128, 16-bit intermediates), else MFA_ERROR_INVALID_ARGS.
+ * No atomics: bitwise repeatable.  In-stream; the row-constant scratch grows on first use (warm up before capturing). */
+mfa_error_t umfa_attention_backward_dropout_stream(mfa_context_t context, void* stream, const void* dout, const void* q,
+                                                   const void* k, const void* v, const void* out, const float* softmax_lse,
+                                                   void* dq, void* dk, void* dv, float* d_buffer, uint32_t batch_size,
+                                                   uint32_t seq_len_q, uint32_t seq_len_kv, uint32_t num_heads,
+                                                   uint16_t head_dim, float softmax_scale, bool causal,
+                                                   int32_t input_precision, int32_t intermediate_precision,
+                                                   bool grads_in_input_type, bool out_in_input_type, float dropout_p,
+                                                   const int64_t* rng_state);
+
+/* MI355X extra: the dropout keep mask itself as 0 / 1 bytes, dense [B, H, Sq, Skv], from the same definition the kernels use
+ * (tests, debugging).  0 < dropout_p < 1 and rng_state non-NULL, else MFA_ERROR_INVALID_ARGS.  In-stream. */
+mfa_error_t umfa_dropout_keep_mask_stream(mfa_context_t context, void* stream, uint8_t* keep, uint32_t batch_size,
+                                          uint32_t num_heads, uint32_t seq_len_q, uint32_t seq_len_kv, float dropout_p,
+                                          const int64_t* rng_state);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

@@ -34,7 +34,8 @@ struct Tuning {
         sync_chunks{1} /* synchronous forward / backward on host-wrapping buffers: head chunks whose upload / kernels / download overlap on side streams (pinned host ranges); 1 = never (the default: one upload, the kernels, one download on the null stream), 0 = by size, n = n chunks.  OPT-IN: one of three runs of tools/lab/sync_chunk_stress.py (pin / unpin per call under heap churn, torch in-process) aborted, profiles/r6/lab_notes.md section 24 */,
         sync_chunked_calls{0} /* read-out for tests: synchronous forwards that took the chunked form */,
         mirror_cache_hits{0} /* read-out for tests: host wrappers whose HBM mirror came from the cache of destroyed wrappers' mirrors (runtime_internal.h MirrorCache) */,
-        no_bwd_mask{0} /* A/B: masked training goes back to torch (read by the Python routing; the masked backward entry itself still works) */;
+        no_bwd_mask{0} /* A/B: masked training goes back to torch (read by the Python routing; the masked backward entry itself still works) */,
+        sdpa_dropout{0} /* SDPA calls with dropout_p > 0 the dropout kernels serve go to them (read by the Python routing; the dropout entries themselves always work) */;
 };
 Tuning& tuning();
 bool set_tuning(const char* name, const char* value);  // false: unknown name or value out of range
@@ -89,6 +90,26 @@ hipError_t launch_bwd_16(const BwdParams& p, hipStream_t stream, const char** na
 // p.mask_kind / ms / win_* describe the mask; p.mask_flags (optional, tensor masks) the tile flags of launch_mask_flags.
 bool bwd_16_mask_supported(const BwdParams& p);
 hipError_t launch_bwd_16_masked(const BwdParams& p, hipStream_t stream, const char** name);
+
+// Attention dropout (fa_dropout.h: the keep mask; fa_fwd_16_drop.hip, fa_bwd_16_drop.hip): bf16 / fp16, head_dim 64 / 128, causal or not,
+// no mask.  rng: device int64[2] = {seed, offset}; thresh / dscale: drop_threshold(p) / drop_scale(thresh).
+struct DropFwdParams : FwdParams {
+    const int64_t* rng;
+    uint32_t thresh;
+    float dscale;
+};
+struct DropBwdParams : BwdParams {
+    const int64_t* rng;
+    uint32_t thresh;
+    float dscale;
+};
+bool fwd_16_dropout_supported(const FwdParams& p);
+hipError_t launch_fwd_16_dropout(const DropFwdParams& p, hipStream_t stream, const char** name);
+bool bwd_16_dropout_supported(const BwdParams& p);
+hipError_t launch_bwd_16_dropout(const DropBwdParams& p, hipStream_t stream, const char** name);
+// keep[B, H, Sq, Skv] as 0 / 1 bytes
+hipError_t launch_dropout_keep_mask(uint8_t* keep, uint32_t B, uint32_t H, uint32_t Sq, uint32_t Skv, const int64_t* rng, uint32_t thresh,
+                                    hipStream_t stream);
 
 // Neighbours of the attention path (fa_aux.hip): rotary rotation and group-wise Hadamard transform.
 struct RopeParams {

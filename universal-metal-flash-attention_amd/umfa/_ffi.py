@@ -172,6 +172,12 @@ def _load_library(path: str | None = None) -> ctypes.CDLL:
             [mfa_context_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, ctypes.c_uint16,
              ctypes.c_float, ctypes.c_bool, _i32, _i32, _i32])
     sig("umfa_last_kernel_name", ctypes.c_char_p, [mfa_context_t])
+    if path is None or hasattr(lib, "umfa_attention_forward_dropout_stream"):  # attention dropout (include/umfa_abi.h)
+        sig("umfa_attention_forward_dropout_stream", mfa_error_t,
+            [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i32, _vp] + _DIMS + [_f32, _b, _i32, _i32, _f32, _vp])
+        sig("umfa_attention_backward_dropout_stream", mfa_error_t,
+            [mfa_context_t, _vp] + [_vp] * 10 + _DIMS + [_f32, _b, _i32, _i32, _b, _b, _f32, _vp])
+        sig("umfa_dropout_keep_mask_stream", mfa_error_t, [mfa_context_t, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _vp])
     if path is None or hasattr(lib, "umfa_release_scratch"):
         sig("umfa_release_scratch", mfa_error_t, [mfa_context_t, _vp, _i32])
     if path is None or hasattr(lib, "umfa_set_option"):  # (tools/ab_inproc.py also loads older builds by explicit path)

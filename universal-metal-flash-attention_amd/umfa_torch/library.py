@@ -23,6 +23,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import dropout as _dropout
 from . import ops
 
 _SUPPORTED = (torch.float32, torch.float16, torch.bfloat16)
@@ -124,7 +125,9 @@ def op_supports(q, k, v, attn_mask, dropout_p, needs_grad: bool, is_causal: bool
     from . import sdpa as _s
     if _s._quant_precision != _s.QUANT_NONE or (is_causal and attn_mask is not None):
         return False
-    if dropout_p > 0.0 or q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+    if dropout_p > 0.0:  # attention dropout: the dropout kernels, where the option sdpa_dropout routes to them (umfa_torch.dropout)
+        return _dropout.served(q, k, v, attn_mask, dropout_p) and _dropout.routing_enabled()
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         return False
     if not (q.is_cuda and k.is_cuda and v.is_cuda) or q.dtype not in _SUPPORTED or k.dtype != q.dtype or v.dtype != q.dtype:
         return False
@@ -164,6 +167,11 @@ def sdpa(query, key, value, attn_mask=None, dropout_p: float = 0.0, is_causal: b
         return native_sdpa(query, key, value, attn_mask=attn_mask, dropout_p=dropout_p, is_causal=is_causal, scale=scale,
                            enable_gqa=enable_gqa)
     sm_scale = float(scale) if scale is not None else float(q.shape[-1]) ** -0.5
+    if dropout_p > 0.0:
+        if not torch.compiler.is_compiling():
+            _bump("total")
+            _bump("fp32_autograd" if needs_grad else "fp32_instream")
+        return torch.ops.umfa.sdpa_forward_dropout(q, k, v, bool(is_causal), sm_scale, float(dropout_p), _dropout.new_rng_state(q.device))[0]
     return torch.ops.umfa.sdpa_forward(q, k, v, attn_mask, bool(is_causal), sm_scale)[0]
 
 

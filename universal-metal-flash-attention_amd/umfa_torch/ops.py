@@ -48,7 +48,7 @@ def release_scratch(stream=None, all_streams: bool = False) -> None:
 # environment: UMFA_FORCE_W64, UMFA_W64_TAU, ...); this module only reads and writes it.
 _OPTION_NAMES = ("softmax_reference", "softmax_tau", "w64_tau", "force_w64", "no_w64", "w64_grid", "w64_skew", "no_mask_flags", "bwd_exact",
                  "bwd_dq", "bwd_persist", "bwd_separate_delta", "no_split", "force_split", "no_dma", "bn64", "pv_fp16", "bwd_ds_store", "no_w64_mask", "ksplit", "no_pipe", "no_w64_mask_lazy", "no_w64_bias", "no_w64_f32_mask", "f32_mask_ratio", "mask_pass_ratio", "no_w64_ragged_mask", "no_mask_realign",
-                 "cast_two_pass", "bwd_ds_lab", "cast_u", "quant_block_wg", "cast_wait_us", "cbal", "cbal_delta", "decode_ks", "sync_chunks", "sync_chunked_calls", "mirror_cache_hits", "no_bwd_mask")
+                 "cast_two_pass", "bwd_ds_lab", "cast_u", "quant_block_wg", "cast_wait_us", "cbal", "cbal_delta", "decode_ks", "sync_chunks", "sync_chunked_calls", "mirror_cache_hits", "no_bwd_mask", "sdpa_dropout")
 
 
 def get_option(name: str) -> str:
@@ -369,6 +369,52 @@ def attention_backward(dout, q, k, v, o32, lse, *, scale: float, causal: bool = 
     if keep_fp32:  # the caller post-processes the gradients in fp32 (RoPE inverse rotation)
         return dq, dk, dv
     return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype)
+
+
+def attention_forward_dropout(q, k, v, dropout_p: float, rng_state: torch.Tensor, *, scale: float, causal: bool = False, out_dtype=None):
+    """O and the undropped LSE [B*H*Sq] of the SDPA with attention dropout (umfa_attention_forward_dropout_stream): q [B,H,Sq,D], k / v
+    [B,H,Skv,D] fp16 / bf16 device tensors with contiguous rows, rng_state a device int64[2] = {seed, offset}.  Asynchronous on torch's
+    current stream."""
+    B, H, Sq, D = q.shape
+    Skv = k.shape[2]
+    out = torch.empty((B, H, Sq, D), dtype=out_dtype or q.dtype, device=q.device)
+    lse = torch.empty((B * H * Sq,), dtype=torch.float32, device=q.device)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    _check_error(_lib.umfa_attention_forward_dropout_stream(
+        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()), ctypes.c_void_p(k.data_ptr()), _i64(k.stride()),
+        ctypes.c_void_p(v.data_ptr()), _i64(v.stride()), ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()),
+        B, Sq, Skv, H, D, float(scale), bool(causal), _PREC[q.dtype], _PREC[q.dtype], float(dropout_p), ctypes.c_void_p(rng_state.data_ptr())))
+    return out, lse
+
+
+def attention_backward_dropout(dout, q, k, v, out, lse, dropout_p: float, rng_state: torch.Tensor, *, scale: float, causal: bool = False,
+                               grads_in_input_type: bool = True):
+    """dQ, dK, dV of attention_forward_dropout (umfa_attention_backward_dropout_stream): contiguous BHSD device tensors, `out` the dropped
+    O the forward returned (operand type or fp32), `lse` its LSE, the forward's dropout_p and rng_state."""
+    B, H, Sq, D = q.shape
+    Skv = k.shape[2]
+    for t in (dout, q, k, v, out, lse):
+        assert t.is_cuda and t.is_contiguous()
+    gdt = q.dtype if grads_in_input_type else torch.float32
+    dq = torch.empty((B, H, Sq, D), dtype=gdt, device=q.device)
+    dk = torch.empty((B, H, Skv, D), dtype=gdt, device=q.device)
+    dv = torch.empty_like(dk)
+    dvec = torch.empty((B * H * Sq,), dtype=torch.float32, device=q.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+    ptrs = (ctypes.c_void_p(t.data_ptr()) for t in (dout, q, k, v, out, lse, dq, dk, dv, dvec))
+    _check_error(_lib.umfa_attention_backward_dropout_stream(
+        context(), stream, *ptrs, B, Sq, Skv, H, D, float(scale), bool(causal), _PREC[q.dtype], _PREC[q.dtype], bool(grads_in_input_type),
+        out.dtype != torch.float32, float(dropout_p), ctypes.c_void_p(rng_state.data_ptr())))
+    return dq, dk, dv
+
+
+def dropout_keep_mask(B: int, H: int, Sq: int, Skv: int, dropout_p: float, rng_state: torch.Tensor) -> torch.Tensor:
+    """The keep mask the dropout kernels apply, as a uint8 [B, H, Sq, Skv] tensor of 0 / 1 (umfa_dropout_keep_mask_stream)."""
+    keep = torch.empty((B, H, Sq, Skv), dtype=torch.uint8, device=rng_state.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(rng_state.device).cuda_stream)
+    _check_error(_lib.umfa_dropout_keep_mask_stream(context(), stream, ctypes.c_void_p(keep.data_ptr()), B, H, Sq, Skv, float(dropout_p),
+                                                    ctypes.c_void_p(rng_state.data_ptr())))
+    return keep
 
 
 def bench_int8(steps: int = 20, warmup: int = 3):

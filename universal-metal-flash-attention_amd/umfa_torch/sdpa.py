@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from umfa._ffi import MFA_PRECISION_INT4, MFA_PRECISION_INT8, _check_error, _lib
 
+from . import dropout as _dropout
 from . import ops
 
 QUANT_NONE, QUANT_INT8, QUANT_INT4 = 0, MFA_PRECISION_INT8, MFA_PRECISION_INT4   # metal_sdpa_backend.h:650-664
@@ -335,6 +336,16 @@ def scaled_dot_product_attention(query, key, value, attn_mask: Optional[torch.Te
                    or q.size(1) != v.size(1) or q.size(3) != k.size(3) or q.size(3) != v.size(3)
                    or q.dtype not in _SUPPORTED or k.dtype != q.dtype or v.dtype != q.dtype
                    or q.size(3) > 1024 or q.size(3) == 0)  # (the reference's own limit: metal_sdpa_backend.cpp:1082-1084)
+    if (dropout_p > 0.0 and not unsupported and attn_mask is None and _quant_precision == QUANT_NONE
+            and _dropout.served(q, k, v, None, dropout_p) and _dropout.routing_enabled()):
+        # attention dropout on the MFMA kernels (option sdpa_dropout, default off): fa_fwd_16_drop / bwd16_*_drop
+        sm = float(scale) if scale is not None else float(q.size(-1)) ** -0.5
+        if q.requires_grad or k.requires_grad or v.requires_grad:
+            _bump("fp32_autograd")
+            return _dropout.dropout_attention(q, k, v, float(dropout_p), causal=bool(is_causal), scale=sm)
+        _bump("fp32_instream")
+        return ops.attention_forward_dropout(q.contiguous(), k.contiguous(), v.contiguous(), float(dropout_p),
+                                             _dropout.new_rng_state(q.device), scale=sm, causal=bool(is_causal))[0]
     if unsupported or dropout_p > 0.0:
         return fallback()
 
