@@ -37,7 +37,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* The library is built with -fvisibility=hidden: the 54 entry points declared between this push and its pop are the ONLY
+/* The library is built with -fvisibility=hidden: the 60 entry points declared between this push and its pop are the ONLY
  * dynamic symbols of libMFAFFI.so (tests/test_abi_symbols.py checks `nm -D`).  Harmless for callers. */
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility push(default)
@@ -419,6 +419,43 @@ mfa_error_t umfa_attention_backward_dropout_stream(mfa_context_t context, void* 
 mfa_error_t umfa_dropout_keep_mask_stream(mfa_context_t context, void* stream, uint8_t* keep, uint32_t batch_size,
                                           uint32_t num_heads, uint32_t seq_len_q, uint32_t seq_len_kv, float dropout_p,
                                           const int64_t* rng_state);
+
+/* MI355X extra: packed variable-length attention (flash-attention's varlen form, torch.nn.attention.varlen.varlen_attn).
+ *   Layout: q [total_q, num_heads, D], k and v [total_k, num_kv_heads, D]; *_strides = {token, head} in ELEMENTS (NULL: dense), both
+ *   multiples of 8, head_dim contiguous, bases 16-byte aligned -- so qkv[:, 0] of a [T, 3, H, D] projection is accepted as it is.
+ *   cu_seq_q, cu_seq_k: DEVICE int32 [num_seqs + 1]; sequence n owns rows cu[n] .. cu[n+1]-1 (zero-length sequences allowed).  The
+ *   offsets are read by the kernels when they run and never by the host: the calls never synchronise, and a captured graph follows the
+ *   CONTENTS of cu_seq_* on replay.  Only num_seqs, total_*, max_q, max_k are host values.
+ *   GQA: num_heads % num_kv_heads == 0, query head h reads KV head h / (num_heads / num_kv_heads).
+ *   Causal is BOTTOM-RIGHT aligned per sequence: query i sees key j iff j <= i + (L_k - L_q) (flash-attention's varlen convention,
+ *   torch.nn.attention.bias.causal_lower_right); with L_q == L_k it is the top-left is_causal of the dense entries.
+ *   A row that sees no key (L_k = 0, or causal with L_q > L_k) gives O = 0 exactly, LSE = -inf, and dQ = 0.
+ *   Memory safety: each sequence's range is clamped on the device into [0, total) and its length to max_q / max_k, so no offsets make the
+ *   kernels read or write outside the tensors; rows of a sequence longer than max_q / max_k, and rows no sequence covers, are undefined.
+ *   Scope: fp16 / bf16, head_dim 64 / 128, softmax_scale > 0 (callers pass D^-0.5 for the default); else MFA_ERROR_INVALID_ARGS.
+ *   Scratch from the stream's pools (bf16: the fp16 V image; backward: row constants): valid under stream capture after a warm-up
+ *   call, a capture that would have to grow a pool returns MFA_ERROR_MEMORY_ALLOCATION.
+ * Forward: out dense [total_q, num_heads, D] in out_precision (fp32 or the input type); lse (optional) fp32 [num_heads, total_q],
+ * natural log (torch's varlen layout). */
+mfa_error_t umfa_varlen_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                 const void* k, const int64_t* k_strides, const void* v, const int64_t* v_strides,
+                                                 const int32_t* cu_seq_q, const int32_t* cu_seq_k, uint32_t num_seqs, uint32_t total_q,
+                                                 uint32_t total_k, uint32_t max_q, uint32_t max_k, uint32_t num_heads,
+                                                 uint32_t num_kv_heads, uint16_t head_dim, float softmax_scale, bool causal,
+                                                 int32_t input_precision, void* out, int32_t out_precision, float* lse);
+
+/* MI355X extra: the backward of umfa_varlen_attention_forward_stream, the same layout and scope.  dout and out dense
+ * [total_q, num_heads, D] (dout in the input type, out in the input type or fp32: out_in_input_type), softmax_lse the forward's
+ * [num_heads, total_q].  dq dense [total_q, num_heads, D], dk and dv dense [total_k, num_kv_heads, D], in the input type or fp32
+ * (grads_in_input_type); grouped query heads are summed inside the dK / dV kernel in a fixed order.  No atomics: bitwise repeatable. */
+mfa_error_t umfa_varlen_attention_backward_stream(mfa_context_t context, void* stream, const void* dout, const void* q,
+                                                  const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                                                  const int64_t* v_strides, const void* out, bool out_in_input_type,
+                                                  const float* softmax_lse, const int32_t* cu_seq_q, const int32_t* cu_seq_k,
+                                                  uint32_t num_seqs, uint32_t total_q, uint32_t total_k, uint32_t max_q, uint32_t max_k,
+                                                  uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, float softmax_scale,
+                                                  bool causal, int32_t input_precision, void* dq, void* dk, void* dv,
+                                                  bool grads_in_input_type);
 
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:

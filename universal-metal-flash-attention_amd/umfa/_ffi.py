@@ -178,6 +178,12 @@ def _load_library(path: str | None = None) -> ctypes.CDLL:
         sig("umfa_attention_backward_dropout_stream", mfa_error_t,
             [mfa_context_t, _vp] + [_vp] * 10 + _DIMS + [_f32, _b, _i32, _i32, _b, _b, _f32, _vp])
         sig("umfa_dropout_keep_mask_stream", mfa_error_t, [mfa_context_t, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _vp])
+    if path is None or hasattr(lib, "umfa_varlen_attention_forward_stream"):  # packed variable-length attention (include/umfa_abi.h)
+        _VL = [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _u16, _f32, _b, _i32]  # cu_seq_q/k, N, T_q, T_k, max_q/k, H, H_kv, D, scale, causal, prec
+        sig("umfa_varlen_attention_forward_stream", mfa_error_t,
+            [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p] + _VL + [_vp, _i32, _vp])
+        sig("umfa_varlen_attention_backward_stream", mfa_error_t,
+            [mfa_context_t, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _b, _vp] + _VL + [_vp, _vp, _vp, _b])
     if path is None or hasattr(lib, "umfa_release_scratch"):
         sig("umfa_release_scratch", mfa_error_t, [mfa_context_t, _vp, _i32])
     if path is None or hasattr(lib, "umfa_set_option"):  # (tools/ab_inproc.py also loads older builds by explicit path)

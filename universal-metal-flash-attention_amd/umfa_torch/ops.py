@@ -520,3 +520,47 @@ def hadamard_rotate(t: torch.Tensor, block_size: int) -> torch.Tensor:
     finally:
         buf.close()
     return t
+
+
+def varlen_attention_forward(q, k, v, cu_seq_q, cu_seq_k, max_q: int, max_k: int, *, scale: float, causal: bool = False, out_dtype=None,
+                             out: Optional[torch.Tensor] = None):
+    """O [T_q, H, D] and LSE [H, T_q] (fp32, natural log) of packed variable-length attention (umfa_varlen_attention_forward_stream):
+    q [T_q, H, D], k / v [T_k, H_kv, D] fp16 / bf16 device tensors with a contiguous head_dim (token / head strides multiples of 8),
+    cu_seq_q / cu_seq_k device int32 [N + 1].  Causal is bottom-right per sequence.  `out`: a caller-allocated dense [T_q, H, D] view
+    to write into.  Asynchronous on torch's current stream; the offsets are never read back."""
+    Tq, H, D = q.shape
+    Tk, Hkv = k.shape[0], k.shape[1]
+    N = cu_seq_q.numel() - 1
+    if out is None:
+        out = torch.empty((Tq, H, D), dtype=out_dtype or q.dtype, device=q.device)
+    lse = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    _check_error(_lib.umfa_varlen_attention_forward_stream(
+        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]), ctypes.c_void_p(k.data_ptr()),
+        _i64(k.stride()[:2]), ctypes.c_void_p(v.data_ptr()), _i64(v.stride()[:2]), ctypes.c_void_p(cu_seq_q.data_ptr()),
+        ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
+        ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr())))
+    return out, lse
+
+
+def varlen_attention_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q: int, max_k: int, *, scale: float, causal: bool = False,
+                              grads_in_input_type: bool = True):
+    """dQ [T_q, H, D], dK / dV [T_k, H_kv, D] of varlen_attention_forward (umfa_varlen_attention_backward_stream): dout and out dense
+    [T_q, H, D] (out in the operand type or fp32), lse the forward's [H, T_q]; q / k / v as the forward takes them."""
+    Tq, H, D = q.shape
+    Tk, Hkv = k.shape[0], k.shape[1]
+    N = cu_seq_q.numel() - 1
+    for t in (dout, out, lse):
+        assert t.is_cuda and t.is_contiguous()
+    gdt = q.dtype if grads_in_input_type else torch.float32
+    dq = torch.empty((Tq, H, D), dtype=gdt, device=q.device)
+    dk = torch.empty((Tk, Hkv, D), dtype=gdt, device=q.device)
+    dv = torch.empty_like(dk)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+    _check_error(_lib.umfa_varlen_attention_backward_stream(
+        context(), stream, ctypes.c_void_p(dout.data_ptr()), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]),
+        ctypes.c_void_p(k.data_ptr()), _i64(k.stride()[:2]), ctypes.c_void_p(v.data_ptr()), _i64(v.stride()[:2]),
+        ctypes.c_void_p(out.data_ptr()), out.dtype != torch.float32, ctypes.c_void_p(lse.data_ptr()), ctypes.c_void_p(cu_seq_q.data_ptr()),
+        ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
+        ctypes.c_void_p(dq.data_ptr()), ctypes.c_void_p(dk.data_ptr()), ctypes.c_void_p(dv.data_ptr()), bool(grads_in_input_type)))
+    return dq, dk, dv
