@@ -37,7 +37,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* The library is built with -fvisibility=hidden: the 60 entry points declared between this push and its pop are the ONLY
+/* The library is built with -fvisibility=hidden: the 61 entry points declared between this push and its pop are the ONLY
  * dynamic symbols of libMFAFFI.so (tests/test_abi_symbols.py checks `nm -D`).  Harmless for callers. */
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility push(default)
@@ -456,6 +456,44 @@ mfa_error_t umfa_varlen_attention_backward_stream(mfa_context_t context, void* s
                                                   uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, float softmax_scale,
                                                   bool causal, int32_t input_precision, void* dq, void* dk, void* dv,
                                                   bool grads_in_input_type);
+
+/* MI355X extra: attention over a paged or static KV cache for inference (flash-attention's flash_attn_with_kvcache), forward only.
+ *   q [batch, seqlen_q, num_heads, D]; q_strides = {batch, token, head} in ELEMENTS (NULL: dense).
+ *   Paged cache (block_table != NULL): k_cache / v_cache [num_pages, page_size, num_kv_heads, D], *_cache_strides = {page, token, head};
+ *   block_table DEVICE int32 [batch][block_table_stride]: sequence b's logical page lp is physical page block_table[b * stride + lp],
+ *   lp < max_pages_per_seq; page_size a multiple of 16.
+ *   Static cache (block_table == NULL): page b is sequence b's whole row of page_size = S_max tokens, so
+ *   [batch, S_max, H_kv, D] and [batch, H_kv, S_max, D] are both taken through their strides ({batch, token, head}), without a copy;
+ *   num_pages and max_pages_per_seq are ignored.
+ *   cache_seqlens DEVICE int32 [batch], contiguous (entry b at cache_seqlens + b): the cached length of each sequence, never read by the
+ *   host.  Every stride is a multiple of 8
+ *   elements with head_dim contiguous; bases 16-byte aligned.
+ *   Append (seqlen_new > 0): k_new / v_new [batch, seqlen_new, num_kv_heads, D] ({batch, token, head} strides) are written into the cache
+ *   in place at positions cache_seqlens[b] .. + seqlen_new - 1, through the block table, on `stream` before the attention; cache_seqlens
+ *   itself is not modified.  Attention then covers L_k = cache_seqlens[b] + seqlen_new keys.
+ *   Causal is BOTTOM-RIGHT aligned per sequence: query i sees key j iff j <= i + L_k - seqlen_q.  A row that sees no key gives O = 0
+ *   exactly and LSE = -inf.  GQA: num_heads % num_kv_heads == 0, query head h reads KV head h / (num_heads / num_kv_heads).
+ *   Memory safety, on the device: cache_seqlens[b] and L_k are clamped into [0, max_pages_per_seq * page_size] (static: [0, S_max]);
+ *   a block-table entry outside [0, num_pages) is never dereferenced -- its keys count as masked and the append skips its rows; append
+ *   rows past the capacity are dropped.  No table or length contents make a kernel touch memory outside q, the cache pools, k_new /
+ *   v_new, out and lse.  Pages shared between sequences may be read; appending into a page another sequence also reads or appends to is
+ *   the caller's race.
+ *   num_splits: 0 = the library picks the split-KV parts from max_pages_per_seq * page_size and the CU count; > 0 forces that many.
+ *   Split partials come from the stream's pooled workspace: valid under stream capture after a warm-up call, a capture that would have
+ *   to grow it returns MFA_ERROR_MEMORY_ALLOCATION.  Never synchronises; a captured graph follows the contents of cache_seqlens and
+ *   block_table on replay.
+ *   Scope: fp16 / bf16, head_dim 64 / 128, softmax_scale > 0; else MFA_ERROR_INVALID_ARGS.
+ * out dense [batch, seqlen_q, num_heads, D] in out_precision (fp32 or the input type); lse (optional) fp32 [batch, num_heads, seqlen_q],
+ * natural log. */
+mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                  void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                  const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                  const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                  int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                  uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                  uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq,
+                                                  float softmax_scale, bool causal, int32_t input_precision, void* out,
+                                                  int32_t out_precision, float* lse, int32_t num_splits);
 
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:

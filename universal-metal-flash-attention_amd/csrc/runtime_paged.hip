@@ -1,0 +1,117 @@
+// runtime_paged.hip -- the C ABI of KV-cache attention for inference (include/umfa_abi.h): umfa_kvcache_attention_forward_stream.
+// In-stream, never synchronising: cache_seqlens and the block table stay on the device (the kernels read them when they run), so a
+// captured graph follows their contents on replay.  Launch order on the stream: the append of k_new / v_new (when given), the attention,
+// and with split-KV the fold.  Split partials come from the stream's pooled workspace (a capture that would have to grow it returns
+// MFA_ERROR_MEMORY_ALLOCATION: warm up first).  Anything outside the kernels' scope is MFA_ERROR_INVALID_ARGS: no silent fall-back.
+#include <string.h>
+
+#include "runtime_internal.h"
+#include "fa_paged.h"
+
+using namespace umfa;
+using namespace umfa_rt;
+
+namespace {
+
+mfa_error_t rc_paged(hipError_t e) {
+    return e == hipSuccess ? MFA_SUCCESS : e == hipErrorInvalidValue ? MFA_ERROR_INVALID_ARGS
+                                         : e == hipErrorOutOfMemory ? MFA_ERROR_MEMORY_ALLOCATION : MFA_ERROR_EXECUTION_FAILED;
+}
+
+int paged_cu_count(int dev) {
+    static int cached[64] = {0};
+    if (dev < 0 || dev >= 64) return 256;
+    if (!cached[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+            (void)hipGetLastError();
+            n = 256;
+        }
+        cached[dev] = n;
+    }
+    return cached[dev];
+}
+
+// split-KV parts when the caller leaves it to the library: enough workgroups for every CU's slots (one workgroup per CU at head_dim 128,
+// two at 64), each part at least two 128-key steps of the capacity, at most 64 parts
+uint32_t paged_auto_splits(const PagedParams& p, int ncu) {
+    const uint64_t items = (uint64_t)p.B * p.Hkv * p.nrb;
+    const uint64_t slots = (uint64_t)ncu * (p.D == 128 ? 1 : 2);
+    if (items >= slots) return 1;
+    uint64_t n = (slots + items - 1) / items;
+    const uint64_t steps = ((uint64_t)p.max_pages * p.page_size + 127) / 128;
+    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
+    n = n < by_len ? n : by_len;
+    return (uint32_t)(n < 64 ? n : 64);
+}
+
+}  // namespace
+
+mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                  void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                  const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                  const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                  int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                  uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                  uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq,
+                                                  float softmax_scale, bool causal, int32_t input_precision, void* out,
+                                                  int32_t out_precision, float* lse, int32_t num_splits) {
+    Context* ctx = as_ctx(context);
+    if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !k_cache_strides || !v_cache_strides) return MFA_ERROR_INVALID_ARGS;
+    if (input_precision != MFA_PRECISION_FP16 && input_precision != MFA_PRECISION_BF16) return MFA_ERROR_INVALID_ARGS;
+    if (out_precision != MFA_PRECISION_FP32 && out_precision != input_precision) return MFA_ERROR_INVALID_ARGS;
+    if (!(softmax_scale > 0.0f) || ((uintptr_t)cache_seqlens & 3) || ((uintptr_t)block_table & 3) || num_splits < 0) return MFA_ERROR_INVALID_ARGS;
+    if (seqlen_new && (!k_new || !v_new || !k_new_strides || !v_new_strides)) return MFA_ERROR_INVALID_ARGS;
+    if (block_table && block_table_stride < (int64_t)max_pages_per_seq) return MFA_ERROR_INVALID_ARGS;
+    PagedParams p;
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.kc = k_cache; p.vc = v_cache; p.kn = k_new; p.vn = v_new; p.bt = block_table; p.seqlens = cache_seqlens;
+    p.out = out; p.lse = lse;
+    p.B = batch; p.Sq = seqlen_q; p.Snew = seqlen_new; p.H = num_heads; p.Hkv = num_kv_heads; p.D = head_dim;
+    p.page_size = page_size;
+    // static cache: page b is sequence b's row of S_max = page_size tokens
+    p.num_pages = block_table ? num_pages : batch;
+    p.max_pages = block_table ? max_pages_per_seq : 1;
+    p.bt_stride = block_table ? block_table_stride : 0;
+    p.page_shift = (page_size && !(page_size & (page_size - 1))) ? __builtin_ctz(page_size) : -1;
+    p.qsb = q_strides ? q_strides[0] : (int64_t)seqlen_q * num_heads * head_dim;
+    p.qst = q_strides ? q_strides[1] : (int64_t)num_heads * head_dim;
+    p.qsh = q_strides ? q_strides[2] : (int64_t)head_dim;
+    p.kpg = k_cache_strides[0]; p.kst = k_cache_strides[1]; p.ksh = k_cache_strides[2];
+    p.vpg = v_cache_strides[0]; p.vst = v_cache_strides[1]; p.vsh = v_cache_strides[2];
+    if (seqlen_new) {
+        p.knb = k_new_strides[0]; p.knt = k_new_strides[1]; p.knh = k_new_strides[2];
+        p.vnb = v_new_strides[0]; p.vnt = v_new_strides[1]; p.vnh = v_new_strides[2];
+    }
+    p.scale = softmax_scale;
+    p.causal = causal ? 1 : 0;
+    p.in_prec = dense_prec(input_precision);
+    p.out_prec = dense_prec(out_precision);
+    if (num_kv_heads == 0 || num_heads % num_kv_heads) return MFA_ERROR_INVALID_ARGS;
+    const uint64_t R = (uint64_t)(num_heads / num_kv_heads) * seqlen_q;
+    if (R >= (1ull << 31)) return MFA_ERROR_INVALID_ARGS;
+    p.R = (uint32_t)R;
+    p.ks4 = R <= 32 ? 1 : 0;
+    p.nrb = p.ks4 ? 1u : (uint32_t)((R + 127) / 128);
+    p.nsplit = 1;
+    if (!paged_supported(p) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
+    const char* name = "none";
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const int dev = stream_device((hipStream_t)stream);
+    DeviceGuard guard(dev);
+    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : paged_auto_splits(p, paged_cu_count(dev));
+    if (!paged_supported(p)) return MFA_ERROR_INVALID_ARGS;
+    if (p.nsplit > 1 && R) {
+        StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
+        const size_t bytes = (size_t)p.nsplit * p.B * p.Hkv * p.R * (p.D + 2) * sizeof(float);
+        p.part = (float*)sc.workspace.ensure(bytes, (hipStream_t)stream);
+        if (!p.part) return MFA_ERROR_MEMORY_ALLOCATION;
+    }
+    if (seqlen_new) {
+        const hipError_t e = launch_paged_append(p, (hipStream_t)stream);
+        if (e != hipSuccess) return rc_paged(e);
+    }
+    const hipError_t e = launch_fwd_16_paged(p, (hipStream_t)stream, &name);
+    ctx->last_kernel = name;
+    return rc_paged(e);
+}

@@ -1,0 +1,146 @@
+"""Attention over a paged or static KV cache for inference, on the 16-bit MFMA kernels: the `umfa::kvcache_forward` custom op (and its
+appending form `umfa::kvcache_forward_append`, which declares the in-place write of k_cache / v_cache so that torch.compile orders it),
+both with fake implementations, and `kvcache_attention`, with the arguments of flash-attention's flash_attn_with_kvcache.
+
+Layout: q [B, Sq, H, D].  Paged cache: k_cache / v_cache [num_pages, page_size, H_kv, D] with block_table int32 [B, max_pages_per_seq]
+(page_size a multiple of 16).  Static cache (block_table None): k_cache / v_cache [B, S_max, H_kv, D], or HF's [B, H_kv, S_max, D] passed
+as its .transpose(1, 2) view -- no copy either way.  cache_seqlens int32 [B] stays on the device: no call synchronises, and a captured
+graph follows its contents and the block table's on replay.  k / v [B, S_new, H_kv, D] are written into the cache at cache_seqlens[b] ..
+before the attention, which then covers cache_seqlens[b] + S_new keys; cache_seqlens itself is not advanced.  Causal is bottom-right
+aligned per sequence.  Lengths and table entries outside the cache are clamped / masked on the device.
+
+Scope: fp16 / bf16 device tensors, head_dim 64 / 128, forward only (a backward through these ops raises).  Anything else raises
+ValueError: there is no fall-back.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import ops
+
+KVCACHE_HEAD_DIMS = (64, 128)
+_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _strides_ok(t: torch.Tensor) -> bool:
+    s = t.stride()
+    # (being traced by torch.compile there is no address to look at: the op checks it when it runs)
+    aligned = torch.compiler.is_compiling() or t.data_ptr() % 16 == 0
+    return s[-1] == 1 and all(x % 8 == 0 and x >= 0 for x in s[:-1]) and aligned
+
+
+def _kernel_view(t: torch.Tensor) -> torch.Tensor:
+    """t itself when the kernels can read it (contiguous head_dim, other strides multiples of 8, 16-byte aligned), else a copy"""
+    return t if _strides_ok(t) and t.stride(1) >= t.shape[-1] else t.contiguous()
+
+
+@torch.library.custom_op("umfa::kvcache_forward", mutates_args=(), device_types="cuda")
+def kvcache_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_seqlens: torch.Tensor,
+                    block_table: Optional[torch.Tensor], causal: bool, scale: float, num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """O [B, Sq, H, D] (q's dtype) and the fp32 log-sum-exp [B, H, Sq] (umfa_kvcache_attention_forward_stream)."""
+    return ops.kvcache_attention_forward(_kernel_view(q), k_cache, v_cache, cache_seqlens, block_table, scale=float(scale),
+                                         causal=bool(causal), num_splits=int(num_splits))
+
+
+@kvcache_forward.register_fake
+def _(q, k_cache, v_cache, cache_seqlens, block_table, causal, scale, num_splits):
+    B, Sq, H, D = q.shape
+    return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
+
+
+@torch.library.custom_op("umfa::kvcache_forward_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def kvcache_forward_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                           cache_seqlens: torch.Tensor, block_table: Optional[torch.Tensor], causal: bool, scale: float,
+                           num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kvcache_forward after writing k / v [B, S_new, H_kv, D] into k_cache / v_cache in place at cache_seqlens[b] .."""
+    return ops.kvcache_attention_forward(_kernel_view(q), k_cache, v_cache, cache_seqlens, block_table, _kernel_view(k), _kernel_view(v),
+                                         scale=float(scale), causal=bool(causal), num_splits=int(num_splits))
+
+
+@kvcache_forward_append.register_fake
+def _(q, k_cache, v_cache, k, v, cache_seqlens, block_table, causal, scale, num_splits):
+    B, Sq, H, D = q.shape
+    return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
+
+
+# flash_attn_with_kvcache arguments this entry accepts only at their defaults
+_UNSUPPORTED = {"rotary_cos": None, "rotary_sin": None, "cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
+                "softcap": 0.0, "alibi_slopes": None}
+
+
+def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table):
+    def bad(msg):
+        raise ValueError(f"kvcache_attention: {msg}")
+
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or not t.is_cuda or t.dtype not in _DTYPES:
+            bad(f"{name} must be a 4-D fp16 / bf16 device tensor (got {getattr(t, 'shape', t)}, {getattr(t, 'dtype', None)})")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or k_cache.shape != v_cache.shape:
+        bad("k_cache and v_cache must match each other in shape and q in dtype")
+    B, Sq, H, D = q.shape
+    Hkv = k_cache.shape[2]
+    if D not in KVCACHE_HEAD_DIMS or k_cache.shape[3] != D:
+        bad(f"head_dim must be 64 or 128 and equal in q and the cache (got {D}, {k_cache.shape[3]})")
+    if Hkv == 0 or H % Hkv:
+        bad(f"num_heads ({H}) must be a multiple of the cache's num_kv_heads ({Hkv})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not _strides_ok(t) or t.stride(1) < D:
+            bad(f"{name} needs a contiguous head_dim and page / token / head strides that are multiples of 8 elements")
+    if block_table is not None:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or not block_table.is_cuda \
+                or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
+            bad("block_table must be a device int32 [batch, max_pages_per_seq] tensor with unit column stride and rows that do not overlap")
+        if k_cache.shape[1] % 16:
+            bad(f"a paged cache's page_size must be a multiple of 16 (got {k_cache.shape[1]})")
+    elif k_cache.shape[0] < B:
+        bad(f"a static cache needs one row per sequence ({k_cache.shape[0]} rows for batch {B})")
+    if (k is None) != (v is None):
+        bad("k and v must be given together")
+    if k is not None:
+        if k.dim() != 4 or k.shape != v.shape or k.shape[0] != B or k.shape[2] != Hkv or k.shape[3] != D or k.dtype != q.dtype \
+                or v.dtype != q.dtype or not k.is_cuda or not v.is_cuda:
+            bad(f"k / v must be [batch, S_new, num_kv_heads, head_dim] in q's dtype (got {tuple(k.shape)}, {tuple(v.shape)})")
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,) or not cache_seqlens.is_cuda:
+        bad("cache_seqlens must be an int, or a device int32 [batch] tensor")
+    # the kernels read cache_seqlens[b] at element b: an expanded (stride 0) or strided view would hand every sequence a wrong length
+    if B > 1 and cache_seqlens.stride(0) != 1:
+        bad(f"cache_seqlens must be contiguous (got stride {cache_seqlens.stride(0)}): pass cache_seqlens.contiguous()")
+
+
+def kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor] = None,
+                      v: Optional[torch.Tensor] = None, cache_seqlens=None, block_table: Optional[torch.Tensor] = None,
+                      softmax_scale: Optional[float] = None, causal: bool = False, num_splits: int = 0,
+                      return_softmax_lse: bool = False, **unsupported):
+    """flash_attn_with_kvcache on the MFMA kernels: softmax(q k^T scale [bottom-right causal]) v over each sequence's cached keys,
+    after appending k / v into the cache in place.  Returns O [B, Sq, H, D] in q's dtype, or (O, LSE [B, H, Sq] fp32) with
+    return_softmax_lse.  cache_seqlens: an int (broadcast to every sequence) or a device int32 [B]; None = the whole capacity.
+    rotary_cos / rotary_sin / cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes are accepted at their defaults only.
+    Raises ValueError outside the kernels' scope (see the module docstring)."""
+    for name, val in unsupported.items():
+        if name not in _UNSUPPORTED and name != "rotary_interleaved":
+            raise TypeError(f"kvcache_attention() got an unexpected keyword argument '{name}'")
+        if name == "rotary_interleaved":
+            continue  # (only meaningful with rotary_cos, which is refused below)
+        default = _UNSUPPORTED[name]
+        same = val is None if default is None else (tuple(val) == default if name == "window_size" else val == default)
+        if not same:
+            raise ValueError(f"kvcache_attention: {name} is not supported (only its default, {default!r}, is accepted)")
+    if isinstance(q, torch.Tensor) and q.dim() == 4:
+        B = q.shape[0]
+        cap = k_cache.shape[1] * (block_table.shape[1] if isinstance(block_table, torch.Tensor) and block_table.dim() == 2 else 1)
+        if cache_seqlens is None:
+            cache_seqlens = cap
+        if isinstance(cache_seqlens, int):
+            cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+    if not isinstance(cache_seqlens, torch.Tensor):
+        raise ValueError("kvcache_attention: cache_seqlens must be an int, or a device int32 [batch] tensor")
+    _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table)
+    sm = float(softmax_scale) if softmax_scale is not None else float(q.shape[-1]) ** -0.5
+    if k is not None and k.shape[1] > 0:
+        out, lse = torch.ops.umfa.kvcache_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, block_table, bool(causal), sm,
+                                                         int(num_splits))
+    else:
+        out, lse = torch.ops.umfa.kvcache_forward(q, k_cache, v_cache, cache_seqlens, block_table, bool(causal), sm, int(num_splits))
+    return (out, lse) if return_softmax_lse else out

@@ -564,3 +564,34 @@ def varlen_attention_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q
         ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
         ctypes.c_void_p(dq.data_ptr()), ctypes.c_void_p(dk.data_ptr()), ctypes.c_void_p(dv.data_ptr()), bool(grads_in_input_type)))
     return dq, dk, dv
+
+
+def kvcache_attention_forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_new=None, *, scale: float,
+                              causal: bool = False, num_splits: int = 0, out_dtype=None):
+    """O [B, Sq, H, D] and LSE [B, H, Sq] (fp32, natural log) of attention over a paged or static KV cache
+    (umfa_kvcache_attention_forward_stream), appending k_new / v_new [B, S_new, H_kv, D] into the cache in place first.
+    q [B, Sq, H, D]; paged: k_cache / v_cache [num_pages, page_size, H_kv, D] with block_table device int32 [B, max_pages]; static
+    (block_table None): k_cache / v_cache [B, S_max, H_kv, D] -- HF's [B, H_kv, S_max, D] as its .transpose(1, 2) view, no copy.
+    cache_seqlens device int32 [B].  fp16 / bf16 with a contiguous head_dim and strides that are multiples of 8 elements.  Asynchronous
+    on torch's current stream; cache_seqlens and block_table are never read back."""
+    B, Sq, H, D = q.shape
+    if B > 1 and (cache_seqlens.stride(0) != 1 or (block_table is not None and block_table.stride(1) != 1)):
+        raise ValueError("kvcache_attention_forward: cache_seqlens and the rows of block_table must be contiguous")
+    num_pages, page_size, Hkv = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    if block_table is not None:
+        max_pages, bt_stride, bt = block_table.shape[1], block_table.stride(0), ctypes.c_void_p(block_table.data_ptr())
+    else:
+        max_pages, bt_stride, bt = 1, 0, None
+    Snew = 0 if k_new is None else k_new.shape[1]
+    out = torch.empty((B, Sq, H, D), dtype=out_dtype or q.dtype, device=q.device)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    new = [None, None, None, None]
+    if Snew:
+        new = [ctypes.c_void_p(k_new.data_ptr()), _i64(k_new.stride()[:3]), ctypes.c_void_p(v_new.data_ptr()), _i64(v_new.stride()[:3])]
+    _check_error(_lib.umfa_kvcache_attention_forward_stream(
+        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:3]), ctypes.c_void_p(k_cache.data_ptr()),
+        _i64(k_cache.stride()[:3]), ctypes.c_void_p(v_cache.data_ptr()), _i64(v_cache.stride()[:3]), *new, bt, int(bt_stride),
+        ctypes.c_void_p(cache_seqlens.data_ptr()), B, Sq, Snew, H, Hkv, D, int(page_size), int(num_pages), int(max_pages), float(scale),
+        bool(causal), _PREC[q.dtype], ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()), int(num_splits)))
+    return out, lse
