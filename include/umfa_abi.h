@@ -457,6 +457,32 @@ mfa_error_t umfa_varlen_attention_backward_stream(mfa_context_t context, void* s
                                                   bool causal, int32_t input_precision, void* dq, void* dk, void* dv,
                                                   bool grads_in_input_type);
 
+/* MI355X extra: umfa_varlen_attention_forward_stream / umfa_varlen_attention_backward_stream with a sliding window, flash-attention's
+ * window_size = (window_left, window_right), bottom-right per sequence.  For sequence n with lengths L_q, L_k and off = L_k - L_q,
+ * query row i sees key j iff 0 <= j < L_k, and (window_left < 0 or j >= i + off - window_left), and
+ * (window_right < 0 or j <= i + off + window_right).  -1 is unbounded on that side; a value below -1 is MFA_ERROR_INVALID_ARGS.
+ * causal sets window_right = 0 (so (left, -1) with causal is a causal look-back window of left keys).  With L_q == L_k this is the
+ * dense sliding window i - left <= j <= i + right.  A row that sees no key gives O = 0 exactly, LSE = -inf and dQ = 0; a key no row
+ * sees gets dK = dV = 0.  The host normalises without touching the device: window_left >= max_k and window_right >= max_q are
+ * unbounded, and a call whose window bounds nothing ((-1, -1), or (-1, 0): bottom-right causal) runs the unwindowed kernels, bit for
+ * bit the unwindowed entries' results.  Everything else as the unwindowed entries; the backward takes the forward's window. */
+mfa_error_t umfa_varlen_attention_forward_window_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                        const void* k, const int64_t* k_strides, const void* v, const int64_t* v_strides,
+                                                        const int32_t* cu_seq_q, const int32_t* cu_seq_k, uint32_t num_seqs,
+                                                        uint32_t total_q, uint32_t total_k, uint32_t max_q, uint32_t max_k,
+                                                        uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, float softmax_scale,
+                                                        bool causal, int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                        int32_t window_left, int32_t window_right);
+
+mfa_error_t umfa_varlen_attention_backward_window_stream(mfa_context_t context, void* stream, const void* dout, const void* q,
+                                                         const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                                                         const int64_t* v_strides, const void* out, bool out_in_input_type,
+                                                         const float* softmax_lse, const int32_t* cu_seq_q, const int32_t* cu_seq_k,
+                                                         uint32_t num_seqs, uint32_t total_q, uint32_t total_k, uint32_t max_q,
+                                                         uint32_t max_k, uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim,
+                                                         float softmax_scale, bool causal, int32_t input_precision, void* dq, void* dk,
+                                                         void* dv, bool grads_in_input_type, int32_t window_left, int32_t window_right);
+
 /* MI355X extra: attention over a paged or static KV cache for inference (flash-attention's flash_attn_with_kvcache), forward only.
  *   q [batch, seqlen_q, num_heads, D]; q_strides = {batch, token, head} in ELEMENTS (NULL: dense).
  *   Paged cache (block_table != NULL): k_cache / v_cache [num_pages, page_size, num_kv_heads, D], *_cache_strides = {page, token, head};

@@ -4,7 +4,8 @@
 //
 // Layout: q [T_q, H, D], k / v [T_k, H_kv, D] with element strides (token, head; head_dim contiguous); out / dO / dQ dense [T_q, H, D],
 // dK / dV dense [T_k, H_kv, D], lse fp32 [H, T_q].  Sequence n owns rows cu[n] .. cu[n+1]-1.  Causal is bottom-right per sequence:
-// query i sees key j iff j <= i + (L_k - L_q).
+// query i sees key j iff j <= i + (L_k - L_q).  The window form (fa_fwd_16_varlen_window.hip, fa_bwd_16_varlen_window.hip) bounds both
+// sides: query i sees key j iff i + (L_k - L_q) - win_left <= j <= i + (L_k - L_q) + win_right (VARLEN_WIN_OPEN: unbounded).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,11 +33,23 @@ struct VarlenParams {
     uint32_t N, H, Hkv, D, Tq, Tk, max_q, max_k;
     float scale;
     int causal, in_prec, out_prec, o_in_type, grad_in_type;
+    int win_left, win_right;  // window kernels only: the band's sides, each in [0, max_k] / [0, max_q] or VARLEN_WIN_OPEN
 };
+
+// an unbounded side of the window kernels' band: i + off +- VARLEN_WIN_OPEN stays inside int32 and past every key (lengths < 2^30)
+constexpr int VARLEN_WIN_OPEN = 1 << 30;
 
 bool varlen_supported(const VarlenParams& p);
 hipError_t launch_fwd_16_varlen(const VarlenParams& p, hipStream_t stream, const char** name);
 hipError_t launch_bwd_16_varlen(const VarlenParams& p, hipStream_t stream, const char** name);
+hipError_t launch_fwd_16_varlen_window(const VarlenParams& p, hipStream_t stream, const char** name);
+hipError_t launch_bwd_16_varlen_window(const VarlenParams& p, hipStream_t stream, const char** name);
+
+// the window bounds the window kernels take (runtime_varlen.hip normalises them so)
+inline bool varlen_window_ok(const VarlenParams& p) {
+    return p.win_left >= 0 && p.win_right >= 0 && (p.win_left == VARLEN_WIN_OPEN || (uint32_t)p.win_left <= p.max_k) &&
+           (p.win_right == VARLEN_WIN_OPEN || (uint32_t)p.win_right <= p.max_q);
+}
 
 namespace {
 

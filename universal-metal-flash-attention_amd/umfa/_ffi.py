@@ -184,6 +184,11 @@ def _load_library(path: str | None = None) -> ctypes.CDLL:
             [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p] + _VL + [_vp, _i32, _vp])
         sig("umfa_varlen_attention_backward_stream", mfa_error_t,
             [mfa_context_t, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _b, _vp] + _VL + [_vp, _vp, _vp, _b])
+    if path is None or hasattr(lib, "umfa_varlen_attention_forward_window_stream"):  # ... with a sliding window (include/umfa_abi.h)
+        sig("umfa_varlen_attention_forward_window_stream", mfa_error_t,
+            [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p] + _VL + [_vp, _i32, _vp, _i32, _i32])
+        sig("umfa_varlen_attention_backward_window_stream", mfa_error_t,
+            [mfa_context_t, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _b, _vp] + _VL + [_vp, _vp, _vp, _b, _i32, _i32])
     if path is None or hasattr(lib, "umfa_kvcache_attention_forward_stream"):  # paged / static KV-cache attention (include/umfa_abi.h)
         sig("umfa_kvcache_attention_forward_stream", mfa_error_t,
             [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,

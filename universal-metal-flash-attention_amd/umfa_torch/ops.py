@@ -7,7 +7,7 @@ the pointers, BHSD element strides, launched on torch's CURRENT stream -- no hos
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -523,11 +523,12 @@ def hadamard_rotate(t: torch.Tensor, block_size: int) -> torch.Tensor:
 
 
 def varlen_attention_forward(q, k, v, cu_seq_q, cu_seq_k, max_q: int, max_k: int, *, scale: float, causal: bool = False, out_dtype=None,
-                             out: Optional[torch.Tensor] = None):
+                             out: Optional[torch.Tensor] = None, window: Optional[Tuple[int, int]] = None):
     """O [T_q, H, D] and LSE [H, T_q] (fp32, natural log) of packed variable-length attention (umfa_varlen_attention_forward_stream):
     q [T_q, H, D], k / v [T_k, H_kv, D] fp16 / bf16 device tensors with a contiguous head_dim (token / head strides multiples of 8),
     cu_seq_q / cu_seq_k device int32 [N + 1].  Causal is bottom-right per sequence.  `out`: a caller-allocated dense [T_q, H, D] view
-    to write into.  Asynchronous on torch's current stream; the offsets are never read back."""
+    to write into.  `window`: (left, right), flash-attention's window_size (umfa_varlen_attention_forward_window_stream; -1 unbounded).
+    Asynchronous on torch's current stream; the offsets are never read back."""
     Tq, H, D = q.shape
     Tk, Hkv = k.shape[0], k.shape[1]
     N = cu_seq_q.numel() - 1
@@ -535,18 +536,21 @@ def varlen_attention_forward(q, k, v, cu_seq_q, cu_seq_k, max_q: int, max_k: int
         out = torch.empty((Tq, H, D), dtype=out_dtype or q.dtype, device=q.device)
     lse = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
     stream = torch.cuda.current_stream(q.device).cuda_stream
-    _check_error(_lib.umfa_varlen_attention_forward_stream(
-        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]), ctypes.c_void_p(k.data_ptr()),
-        _i64(k.stride()[:2]), ctypes.c_void_p(v.data_ptr()), _i64(v.stride()[:2]), ctypes.c_void_p(cu_seq_q.data_ptr()),
-        ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
-        ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr())))
+    args = (context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]), ctypes.c_void_p(k.data_ptr()),
+            _i64(k.stride()[:2]), ctypes.c_void_p(v.data_ptr()), _i64(v.stride()[:2]), ctypes.c_void_p(cu_seq_q.data_ptr()),
+            ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
+            ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()))
+    if window is None:
+        _check_error(_lib.umfa_varlen_attention_forward_stream(*args))
+    else:
+        _check_error(_lib.umfa_varlen_attention_forward_window_stream(*args, int(window[0]), int(window[1])))
     return out, lse
 
 
 def varlen_attention_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q: int, max_k: int, *, scale: float, causal: bool = False,
-                              grads_in_input_type: bool = True):
+                              grads_in_input_type: bool = True, window: Optional[Tuple[int, int]] = None):
     """dQ [T_q, H, D], dK / dV [T_k, H_kv, D] of varlen_attention_forward (umfa_varlen_attention_backward_stream): dout and out dense
-    [T_q, H, D] (out in the operand type or fp32), lse the forward's [H, T_q]; q / k / v as the forward takes them."""
+    [T_q, H, D] (out in the operand type or fp32), lse the forward's [H, T_q]; q / k / v and `window` as the forward takes them."""
     Tq, H, D = q.shape
     Tk, Hkv = k.shape[0], k.shape[1]
     N = cu_seq_q.numel() - 1
@@ -557,12 +561,15 @@ def varlen_attention_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q
     dk = torch.empty((Tk, Hkv, D), dtype=gdt, device=q.device)
     dv = torch.empty_like(dk)
     stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-    _check_error(_lib.umfa_varlen_attention_backward_stream(
-        context(), stream, ctypes.c_void_p(dout.data_ptr()), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]),
-        ctypes.c_void_p(k.data_ptr()), _i64(k.stride()[:2]), ctypes.c_void_p(v.data_ptr()), _i64(v.stride()[:2]),
-        ctypes.c_void_p(out.data_ptr()), out.dtype != torch.float32, ctypes.c_void_p(lse.data_ptr()), ctypes.c_void_p(cu_seq_q.data_ptr()),
-        ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
-        ctypes.c_void_p(dq.data_ptr()), ctypes.c_void_p(dk.data_ptr()), ctypes.c_void_p(dv.data_ptr()), bool(grads_in_input_type)))
+    args = (context(), stream, ctypes.c_void_p(dout.data_ptr()), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]),
+            ctypes.c_void_p(k.data_ptr()), _i64(k.stride()[:2]), ctypes.c_void_p(v.data_ptr()), _i64(v.stride()[:2]),
+            ctypes.c_void_p(out.data_ptr()), out.dtype != torch.float32, ctypes.c_void_p(lse.data_ptr()), ctypes.c_void_p(cu_seq_q.data_ptr()),
+            ctypes.c_void_p(cu_seq_k.data_ptr()), N, Tq, Tk, int(max_q), int(max_k), H, Hkv, D, float(scale), bool(causal), _PREC[q.dtype],
+            ctypes.c_void_p(dq.data_ptr()), ctypes.c_void_p(dk.data_ptr()), ctypes.c_void_p(dv.data_ptr()), bool(grads_in_input_type))
+    if window is None:
+        _check_error(_lib.umfa_varlen_attention_backward_stream(*args))
+    else:
+        _check_error(_lib.umfa_varlen_attention_backward_window_stream(*args, int(window[0]), int(window[1])))
     return dq, dk, dv
 
 

@@ -8,6 +8,11 @@ that are multiples of 8 elements (qkv[:, 0] of a [T, 3, H, D] projection) go to 
 aligned per sequence (query i sees key j iff j <= i + L_k - L_q), flash-attention's varlen convention.  The offsets never leave the
 device: no call synchronises, and a captured graph follows their contents on replay.
 
+Sliding window: `window_size=(left, right)`, flash-attention's convention, bottom-right per sequence -- query i sees key j iff
+j >= i + (L_k - L_q) - left (left >= 0) and j <= i + (L_k - L_q) + right (right >= 0); -1 is unbounded on that side and causal sets
+right = 0.  `umfa::varlen_window_forward` / `umfa::varlen_window_backward` run it; a window that bounds nothing (left >= max_k,
+right >= max_q, or -1) takes the unwindowed ops, bit for bit.
+
 Scope: fp16 / bf16 device tensors, head_dim 64 / 128.  Anything else raises ValueError: there is no fall-back.
 """
 from __future__ import annotations
@@ -90,13 +95,84 @@ def _backward(ctx, dout, dlse):
 varlen_forward.register_autograd(_backward, setup_context=_setup_context)
 
 
+@torch.library.custom_op("umfa::varlen_window_forward", mutates_args=(), device_types="cuda")
+def varlen_window_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seq_q: torch.Tensor, cu_seq_k: torch.Tensor, max_q: int,
+                          max_k: int, is_causal: bool, scale: float, window_left: int,
+                          window_right: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """varlen_forward with a sliding window (umfa_varlen_attention_forward_window_stream)."""
+    return ops.varlen_attention_forward(_kernel_view(q), _kernel_view(k), _kernel_view(v), cu_seq_q.contiguous(), cu_seq_k.contiguous(),
+                                        int(max_q), int(max_k), scale=float(scale), causal=bool(is_causal),
+                                        window=(int(window_left), int(window_right)))
+
+
+@varlen_window_forward.register_fake
+def _(q, k, v, cu_seq_q, cu_seq_k, max_q, max_k, is_causal, scale, window_left, window_right):
+    Tq, H, D = q.shape
+    return q.new_empty((Tq, H, D)), q.new_empty((H, Tq), dtype=torch.float32)
+
+
+@torch.library.custom_op("umfa::varlen_window_backward", mutates_args=(), device_types="cuda")
+def varlen_window_backward(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, lse: torch.Tensor,
+                           cu_seq_q: torch.Tensor, cu_seq_k: torch.Tensor, max_q: int, max_k: int, is_causal: bool, scale: float,
+                           window_left: int, window_right: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """varlen_backward with a sliding window (umfa_varlen_attention_backward_window_stream)."""
+    return ops.varlen_attention_backward(dout.to(q.dtype).contiguous(), _kernel_view(q), _kernel_view(k), _kernel_view(v), out.contiguous(),
+                                         lse.contiguous(), cu_seq_q.contiguous(), cu_seq_k.contiguous(), int(max_q), int(max_k),
+                                         scale=float(scale), causal=bool(is_causal), window=(int(window_left), int(window_right)))
+
+
+@varlen_window_backward.register_fake
+def _(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q, max_k, is_causal, scale, window_left, window_right):
+    return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
+
+
+def _setup_context_window(ctx, inputs, output):
+    _setup_context(ctx, inputs[:9], output)
+    ctx.window = (int(inputs[9]), int(inputs[10]))
+
+
+def _backward_window(ctx, dout, dlse):
+    q, k, v, out, lse, cu_seq_q, cu_seq_k = ctx.saved_tensors
+    dq, dk, dv = torch.ops.umfa.varlen_window_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, ctx.max_q, ctx.max_k, ctx.is_causal,
+                                                       ctx.scale, *ctx.window)
+    return dq, dk, dv, None, None, None, None, None, None, None, None
+
+
+varlen_window_forward.register_autograd(_backward_window, setup_context=_setup_context_window)
+
+
+def _window(window_size, is_causal: bool, max_q: int, max_k: int) -> Tuple[int, int]:
+    """window_size normalised as the C entries do it: causal sets right = 0, a side that cannot bound any row (left >= max_k,
+    right >= max_q) is -1; a value below -1 is a ValueError"""
+    try:
+        left, right = (int(w) for w in window_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"varlen_attention: window_size must be a pair of ints (got {window_size!r})") from None
+    if left < -1 or right < -1:
+        raise ValueError(f"varlen_attention: window_size values must be >= -1 (-1: unbounded), got {(left, right)}")
+    if is_causal:
+        right = 0
+    if left >= max_k:
+        left = -1
+    if right >= max_q:
+        right = -1
+    return left, right
+
+
 def varlen_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, cu_seq_q: torch.Tensor, cu_seq_k: torch.Tensor,
-                     max_q: int, max_k: int, is_causal: bool = False, *, scale: Optional[float] = None, return_lse: bool = False):
+                     max_q: int, max_k: int, is_causal: bool = False, *, scale: Optional[float] = None, return_lse: bool = False,
+                     window_size: Tuple[int, int] = (-1, -1)):
     """softmax(q k^T scale [bottom-right causal]) v per packed sequence -- differentiable in query, key and value.  Returns O [T_q, H, D]
-    in query's dtype, or (O, LSE [H, T_q] fp32, natural log) with return_lse.  A row that sees no key (L_k = 0, or causal with
-    L_q > L_k) gives O = 0 and LSE = -inf.  max_q / max_k: the longest query / key sequence (host ints; rows past them are not computed).
+    in query's dtype, or (O, LSE [H, T_q] fp32, natural log) with return_lse.  A row that sees no key (L_k = 0, causal with L_q > L_k,
+    or outside its window) gives O = 0 and LSE = -inf.  max_q / max_k: the longest query / key sequence (host ints; rows past them are
+    not computed).  window_size: (left, right) sliding window, flash-attention's convention (see the module docstring).
     Raises ValueError outside the kernels' scope (see the module docstring)."""
     _check(query, key, value, cu_seq_q, cu_seq_k)
+    left, right = _window(window_size, bool(is_causal), int(max_q), int(max_k))
     sm = float(scale) if scale is not None else float(query.shape[-1]) ** -0.5
-    out, lse = torch.ops.umfa.varlen_forward(query, key, value, cu_seq_q, cu_seq_k, int(max_q), int(max_k), bool(is_causal), sm)
+    if left == -1 and right in (-1, 0):  # no band: the unwindowed kernels ((-1, 0) is bottom-right causal)
+        out, lse = torch.ops.umfa.varlen_forward(query, key, value, cu_seq_q, cu_seq_k, int(max_q), int(max_k), right == 0, sm)
+    else:
+        out, lse = torch.ops.umfa.varlen_window_forward(query, key, value, cu_seq_q, cu_seq_k, int(max_q), int(max_k), bool(is_causal), sm,
+                                                        left, right)
     return (out, lse) if return_lse else out
