@@ -521,6 +521,32 @@ mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* s
                                                   float softmax_scale, bool causal, int32_t input_precision, void* out,
                                                   int32_t out_precision, float* lse, int32_t num_splits);
 
+/* MI355X extra: umfa_kvcache_attention_forward_stream over an fp8 KV cache.  k_cache / v_cache hold OCP e4m3fn bytes (gfx950's fp8, torch's
+ * float8_e4m3fn; not e4m3fnuz, not e5m2), both of them; q, k_new / v_new and out stay fp16 / bf16 (input_precision describes q and k_new /
+ * v_new).  k_descale / v_descale: DEVICE fp32, entry (b, h_kv) at descale[b * strides[0] + h_kv * strides[1]] with ELEMENT strides >= 0 that
+ * may be 0 (a scalar, [H_kv], [B, 1], [B, H_kv]); never read by the host, so a captured graph follows their contents on replay.  The value
+ * a cache byte stands for is e4m3fn(byte) * descale[b, h_kv], and the call computes
+ *   softmax(q (K8 k_descale)^T softmax_scale [bottom-right causal]) (V8 v_descale),
+ * LSE that of the dequantised scores; the expansions to the 16-bit operand types are exact and the arithmetic is the 16-bit entry's.
+ *   Append: element x of k_new / v_new is stored as e4m3fn_rne(clamp(fp32(x) / descale[b, h_kv], -448, +448)) -- IEEE fp32 division, the
+ *   clamp before the conversion, round to nearest even (bit for bit torch's (x.float() / d).clamp(-448, 448).to(float8_e4m3fn)).  NaN
+ *   inputs and descales that are zero, negative or non-finite give unspecified values but never touch memory outside the pools.
+ *   Cache strides are in elements = bytes: multiples of 16 with head_dim contiguous, bases 16-byte aligned; q / k_new / v_new strides as
+ *   in the 16-bit entry.  Every layout, clamp, masking and memory-safety rule, num_splits, the pooled split workspace, the capture rule
+ *   and the error codes are umfa_kvcache_attention_forward_stream's.  Scope: head_dim 64 / 128, page_size a multiple of 16; anything
+ *   else MFA_ERROR_INVALID_ARGS -- no fall-back. */
+mfa_error_t umfa_kvcache_attention_fp8_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                      void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                      const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                      const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                      int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                      uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                      uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                                      uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                      int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                      int32_t num_splits, const float* k_descale, const int64_t* k_descale_strides,
+                                                      const float* v_descale, const int64_t* v_descale_strides);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

@@ -461,6 +461,20 @@ hipError_t launch_paged_append(const PagedParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// the fold of p.nsplit parts in p.part into p.out (fp32 or the 16-bit p.in_prec) and p.lse; the partials are fp32 whatever the cache
+// holds, so fa_fwd_16_paged_fp8.hip launches it too
+hipError_t launch_paged_fold(const PagedParams& p, hipStream_t stream) {
+    const uint32_t rows = p.B * p.Hkv * p.R, rpb = 256 / (p.D / 4);
+    const dim3 grid((rows + rpb - 1) / rpb);
+    if (p.out_prec == P_FP32)
+        hipLaunchKernelGGL(fa_paged_fold_kernel<float>, grid, dim3(256), 0, stream, p);
+    else if (p.in_prec == P_BF16)
+        hipLaunchKernelGGL(fa_paged_fold_kernel<__bf16>, grid, dim3(256), 0, stream, p);
+    else
+        hipLaunchKernelGGL(fa_paged_fold_kernel<_Float16>, grid, dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
 template <typename T, bool CAUSAL, int DP, typename OUT>
 static hipError_t launch_fwd16_paged_t(const PagedParams& p, hipStream_t stream) {
     constexpr int TILE_BYTES = 32 * 2 * DP;
@@ -468,14 +482,7 @@ static hipError_t launch_fwd16_paged_t(const PagedParams& p, hipStream_t stream)
     if (hipError_t e = ensure_dynamic_lds((const void*)fa_fwd16_paged_kernel<T, CAUSAL, DP, OUT>, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL((fa_fwd16_paged_kernel<T, CAUSAL, DP, OUT>), dim3(p.B * p.Hkv * p.nrb * p.nsplit), dim3(256), lds, stream, p);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    if constexpr (std::is_same<OUT, void>::value) {
-        const uint32_t rows = p.B * p.Hkv * p.R, rpb = 256 / (DP / 4);
-        if (p.out_prec == P_FP32)
-            hipLaunchKernelGGL(fa_paged_fold_kernel<float>, dim3((rows + rpb - 1) / rpb), dim3(256), 0, stream, p);
-        else
-            hipLaunchKernelGGL(fa_paged_fold_kernel<T>, dim3((rows + rpb - 1) / rpb), dim3(256), 0, stream, p);
-        return hipGetLastError();
-    }
+    if constexpr (std::is_same<OUT, void>::value) return launch_paged_fold(p, stream);
     return hipSuccess;
 }
 

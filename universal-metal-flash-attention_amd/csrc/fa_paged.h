@@ -44,6 +44,7 @@ struct PagedParams {
 bool paged_supported(const PagedParams& p);
 hipError_t launch_paged_append(const PagedParams& p, hipStream_t stream);
 hipError_t launch_fwd_16_paged(const PagedParams& p, hipStream_t stream, const char** name);
+hipError_t launch_paged_fold(const PagedParams& p, hipStream_t stream);  // the split-KV fold alone (p.nsplit parts in p.part)
 
 namespace {
 

@@ -1,4 +1,5 @@
-// runtime_paged.hip -- the C ABI of KV-cache attention for inference (include/umfa_abi.h): umfa_kvcache_attention_forward_stream.
+// runtime_paged.hip -- the C ABI of KV-cache attention for inference (include/umfa_abi.h): umfa_kvcache_attention_forward_stream and, over an
+// fp8 (e4m3fn) cache with per-(batch, KV head) descales (fa_paged_fp8.h), umfa_kvcache_attention_fp8_forward_stream.
 // In-stream, never synchronising: cache_seqlens and the block table stay on the device (the kernels read them when they run), so a
 // captured graph follows their contents on replay.  Launch order on the stream: the append of k_new / v_new (when given), the attention,
 // and with split-KV the fold.  Split partials come from the stream's pooled workspace (a capture that would have to grow it returns
@@ -6,7 +7,7 @@
 #include <string.h>
 
 #include "runtime_internal.h"
-#include "fa_paged.h"
+#include "fa_paged_fp8.h"
 
 using namespace umfa;
 using namespace umfa_rt;
@@ -47,15 +48,16 @@ uint32_t paged_auto_splits(const PagedParams& p, int ncu) {
 
 }  // namespace
 
-mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
-                                                  void* k_cache, const int64_t* k_cache_strides, void* v_cache,
-                                                  const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
-                                                  const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
-                                                  int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
-                                                  uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
-                                                  uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq,
-                                                  float softmax_scale, bool causal, int32_t input_precision, void* out,
-                                                  int32_t out_precision, float* lse, int32_t num_splits) {
+namespace {
+
+// both entries: fp8 = the cache is e4m3fn with the descales in f8 (cache strides in bytes), else 16-bit in input_precision
+mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache,
+                            const int64_t* k_cache_strides, void* v_cache, const int64_t* v_cache_strides, const void* k_new,
+                            const int64_t* k_new_strides, const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                            int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch, uint32_t seqlen_q,
+                            uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
+                            uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision,
+                            void* out, int32_t out_precision, float* lse, int32_t num_splits, bool fp8, PagedFp8Params f8) {
     Context* ctx = as_ctx(context);
     if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !k_cache_strides || !v_cache_strides) return MFA_ERROR_INVALID_ARGS;
     if (input_precision != MFA_PRECISION_FP16 && input_precision != MFA_PRECISION_BF16) return MFA_ERROR_INVALID_ARGS;
@@ -63,7 +65,7 @@ mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* s
     if (!(softmax_scale > 0.0f) || ((uintptr_t)cache_seqlens & 3) || ((uintptr_t)block_table & 3) || num_splits < 0) return MFA_ERROR_INVALID_ARGS;
     if (seqlen_new && (!k_new || !v_new || !k_new_strides || !v_new_strides)) return MFA_ERROR_INVALID_ARGS;
     if (block_table && block_table_stride < (int64_t)max_pages_per_seq) return MFA_ERROR_INVALID_ARGS;
-    PagedParams p;
+    PagedParams& p = f8.p;
     memset(&p, 0, sizeof(p));
     p.q = q; p.kc = k_cache; p.vc = v_cache; p.kn = k_new; p.vn = v_new; p.bt = block_table; p.seqlens = cache_seqlens;
     p.out = out; p.lse = lse;
@@ -94,13 +96,14 @@ mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* s
     p.ks4 = R <= 32 ? 1 : 0;
     p.nrb = p.ks4 ? 1u : (uint32_t)((R + 127) / 128);
     p.nsplit = 1;
-    if (!paged_supported(p) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
+    auto supported = [&]() { return fp8 ? paged_fp8_supported(f8) : paged_supported(p); };
+    if (!supported() || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
     const char* name = "none";
     std::lock_guard<std::mutex> lock(ctx->mu);
     const int dev = stream_device((hipStream_t)stream);
     DeviceGuard guard(dev);
     p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : paged_auto_splits(p, paged_cu_count(dev));
-    if (!paged_supported(p)) return MFA_ERROR_INVALID_ARGS;
+    if (!supported()) return MFA_ERROR_INVALID_ARGS;
     if (p.nsplit > 1 && R) {
         StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
         const size_t bytes = (size_t)p.nsplit * p.B * p.Hkv * p.R * (p.D + 2) * sizeof(float);
@@ -108,10 +111,49 @@ mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* s
         if (!p.part) return MFA_ERROR_MEMORY_ALLOCATION;
     }
     if (seqlen_new) {
-        const hipError_t e = launch_paged_append(p, (hipStream_t)stream);
+        const hipError_t e = fp8 ? launch_paged_fp8_append(f8, (hipStream_t)stream) : launch_paged_append(p, (hipStream_t)stream);
         if (e != hipSuccess) return rc_paged(e);
     }
-    const hipError_t e = launch_fwd_16_paged(p, (hipStream_t)stream, &name);
+    const hipError_t e = fp8 ? launch_fwd_16_paged_fp8(f8, (hipStream_t)stream, &name) : launch_fwd_16_paged(p, (hipStream_t)stream, &name);
     ctx->last_kernel = name;
     return rc_paged(e);
+}
+
+}  // namespace
+
+mfa_error_t umfa_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                  void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                  const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                  const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                  int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                  uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                  uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq,
+                                                  float softmax_scale, bool causal, int32_t input_precision, void* out,
+                                                  int32_t out_precision, float* lse, int32_t num_splits) {
+    return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,
+                           v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
+                           num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
+                           out_precision, lse, num_splits, false, PagedFp8Params{});
+}
+
+mfa_error_t umfa_kvcache_attention_fp8_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                      void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                      const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                      const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                      int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                      uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                      uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                                      uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                      int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                      int32_t num_splits, const float* k_descale, const int64_t* k_descale_strides,
+                                                      const float* v_descale, const int64_t* v_descale_strides) {
+    if (!k_descale || !v_descale || !k_descale_strides || !v_descale_strides) return MFA_ERROR_INVALID_ARGS;
+    PagedFp8Params f8;
+    memset(&f8, 0, sizeof(f8));
+    f8.kd = k_descale; f8.kdb = k_descale_strides[0]; f8.kdh = k_descale_strides[1];
+    f8.vd = v_descale; f8.vdb = v_descale_strides[0]; f8.vdh = v_descale_strides[1];
+    return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,
+                           v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
+                           num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
+                           out_precision, lse, num_splits, true, f8);
 }

@@ -193,6 +193,10 @@ def _load_library(path: str | None = None) -> ctypes.CDLL:
         sig("umfa_kvcache_attention_forward_stream", mfa_error_t,
             [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,
              _u32, _u32, _u32, _u32, _u32, _u16, _u32, _u32, _u32, _f32, _b, _i32, _vp, _i32, _vp, _i32])
+    if path is None or hasattr(lib, "umfa_kvcache_attention_fp8_forward_stream"):  # ... over an fp8 (e4m3fn) cache (include/umfa_abi.h)
+        sig("umfa_kvcache_attention_fp8_forward_stream", mfa_error_t,
+            [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,
+             _u32, _u32, _u32, _u32, _u32, _u16, _u32, _u32, _u32, _f32, _b, _i32, _vp, _i32, _vp, _i32, _vp, _i64p, _vp, _i64p])
     if path is None or hasattr(lib, "umfa_release_scratch"):
         sig("umfa_release_scratch", mfa_error_t, [mfa_context_t, _vp, _i32])
     if path is None or hasattr(lib, "umfa_set_option"):  # (tools/ab_inproc.py also loads older builds by explicit path)

@@ -9,8 +9,13 @@ graph follows its contents and the block table's on replay.  k / v [B, S_new, H_
 before the attention, which then covers cache_seqlens[b] + S_new keys; cache_seqlens itself is not advanced.  Causal is bottom-right
 aligned per sequence.  Lengths and table entries outside the cache are clamped / masked on the device.
 
-Scope: fp16 / bf16 device tensors, head_dim 64 / 128, forward only (a backward through these ops raises).  Anything else raises
-ValueError: there is no fall-back.
+fp8 caches: k_cache / v_cache may both be torch.float8_e4m3fn (OCP e4m3fn, gfx950's fp8) with k_descale /
+v_descale, device fp32 tensors that broadcast to [B, H_kv] (a Python float becomes a one-element device tensor): a cache byte stands for
+e4m3fn(byte) * descale[b, h_kv], k / v are quantised on the way in, q and O stay 16-bit.  The `umfa::kvcache_fp8_forward` /
+`umfa::kvcache_fp8_forward_append` ops serve them.  The descales stay on the device like the lengths.
+
+Scope: fp16 / bf16 device tensors (fp8 caches as above), head_dim 64 / 128, forward only (a backward through these ops raises).  Anything
+else raises ValueError: there is no fall-back.
 """
 from __future__ import annotations
 
@@ -28,7 +33,8 @@ def _strides_ok(t: torch.Tensor) -> bool:
     s = t.stride()
     # (being traced by torch.compile there is no address to look at: the op checks it when it runs)
     aligned = torch.compiler.is_compiling() or t.data_ptr() % 16 == 0
-    return s[-1] == 1 and all(x % 8 == 0 and x >= 0 for x in s[:-1]) and aligned
+    gran = 16 // t.element_size()  # 16-byte granules: 8 elements of a 16-bit tensor, 16 of an fp8 one
+    return s[-1] == 1 and all(x % gran == 0 and x >= 0 for x in s[:-1]) and aligned
 
 
 def _kernel_view(t: torch.Tensor) -> torch.Tensor:
@@ -65,20 +71,57 @@ def _(q, k_cache, v_cache, k, v, cache_seqlens, block_table, causal, scale, num_
     return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
 
 
+@torch.library.custom_op("umfa::kvcache_fp8_forward", mutates_args=(), device_types="cuda")
+def kvcache_fp8_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cache_seqlens: torch.Tensor,
+                        k_descale: torch.Tensor, v_descale: torch.Tensor, block_table: Optional[torch.Tensor], causal: bool, scale: float,
+                        num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kvcache_forward over float8_e4m3fn caches with device fp32 descales (umfa_kvcache_attention_fp8_forward_stream).  k_cache /
+    v_cache are the caches' BYTES, their .view(torch.uint8): torch's own op checks (opcheck's schema test, which compares arguments
+    before and after a call) have no float8 kernels to run on."""
+    return ops.kvcache_attention_fp8_forward(_kernel_view(q), k_cache.view(torch.float8_e4m3fn), v_cache.view(torch.float8_e4m3fn),
+                                             cache_seqlens, k_descale, v_descale, block_table, scale=float(scale), causal=bool(causal), num_splits=int(num_splits))
+
+
+@kvcache_fp8_forward.register_fake
+def _(q, k_cache, v_cache, cache_seqlens, k_descale, v_descale, block_table, causal, scale, num_splits):
+    B, Sq, H, D = q.shape
+    return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
+
+
+@torch.library.custom_op("umfa::kvcache_fp8_forward_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def kvcache_fp8_forward_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                               cache_seqlens: torch.Tensor, k_descale: torch.Tensor, v_descale: torch.Tensor,
+                               block_table: Optional[torch.Tensor], causal: bool, scale: float,
+                               num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kvcache_fp8_forward after quantising k / v [B, S_new, H_kv, D] (q's dtype) into k_cache / v_cache (uint8 views, written in place)
+    at cache_seqlens[b] .."""
+    return ops.kvcache_attention_fp8_forward(_kernel_view(q), k_cache.view(torch.float8_e4m3fn), v_cache.view(torch.float8_e4m3fn),
+                                             cache_seqlens, k_descale, v_descale, block_table, _kernel_view(k), _kernel_view(v), scale=float(scale), causal=bool(causal),
+                                             num_splits=int(num_splits))
+
+
+@kvcache_fp8_forward_append.register_fake
+def _(q, k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, block_table, causal, scale, num_splits):
+    B, Sq, H, D = q.shape
+    return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
+
+
 # flash_attn_with_kvcache arguments this entry accepts only at their defaults
 _UNSUPPORTED = {"rotary_cos": None, "rotary_sin": None, "cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
                 "softcap": 0.0, "alibi_slopes": None}
 
 
-def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table):
+def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table, fp8=False):
     def bad(msg):
         raise ValueError(f"kvcache_attention: {msg}")
 
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 4 or not t.is_cuda or t.dtype not in _DTYPES:
-            bad(f"{name} must be a 4-D fp16 / bf16 device tensor (got {getattr(t, 'shape', t)}, {getattr(t, 'dtype', None)})")
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or k_cache.shape != v_cache.shape:
-        bad("k_cache and v_cache must match each other in shape and q in dtype")
+        ok = (torch.float8_e4m3fn,) if fp8 and name != "q" else _DTYPES
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or not t.is_cuda or t.dtype not in ok:
+            bad(f"{name} must be a 4-D fp16 / bf16 device tensor, or the caches both float8_e4m3fn (got {getattr(t, 'shape', t)}, "
+                f"{getattr(t, 'dtype', None)})")
+    if k_cache.dtype != v_cache.dtype or (not fp8 and k_cache.dtype != q.dtype) or k_cache.shape != v_cache.shape:
+        bad("k_cache and v_cache must match each other in shape and dtype, and q in dtype unless they are float8_e4m3fn")
     B, Sq, H, D = q.shape
     Hkv = k_cache.shape[2]
     if D not in KVCACHE_HEAD_DIMS or k_cache.shape[3] != D:
@@ -87,7 +130,7 @@ def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table):
         bad(f"num_heads ({H}) must be a multiple of the cache's num_kv_heads ({Hkv})")
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if not _strides_ok(t) or t.stride(1) < D:
-            bad(f"{name} needs a contiguous head_dim and page / token / head strides that are multiples of 8 elements")
+            bad(f"{name} needs a contiguous head_dim, page / token / head strides that are multiples of 16 bytes and a 16-byte aligned base")
     if block_table is not None:
         if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or not block_table.is_cuda \
                 or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
@@ -109,13 +152,32 @@ def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table):
         bad(f"cache_seqlens must be contiguous (got stride {cache_seqlens.stride(0)}): pass cache_seqlens.contiguous()")
 
 
+def _descale(d, q, Hkv, name):
+    """a descale argument as the device fp32 tensor the op takes: None = 1.0, a Python number becomes a one-element tensor (a fill on
+    the device, no synchronisation), a tensor must be device fp32 and broadcast to [B, H_kv]"""
+    if d is None or isinstance(d, (int, float)):
+        return torch.full((1,), 1.0 if d is None else float(d), dtype=torch.float32, device=q.device)
+    if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.device != q.device or d.dim() > 2:
+        raise ValueError(f"kvcache_attention: {name} must be a float or an fp32 tensor on q's device that broadcasts to [batch, num_kv_heads]")
+    try:
+        torch.broadcast_shapes(tuple(d.shape), (q.shape[0], Hkv))
+    except RuntimeError:
+        raise ValueError(f"kvcache_attention: {name} {tuple(d.shape)} does not broadcast to [{q.shape[0]}, {Hkv}]") from None
+    if d.dim() == 2 and (d.shape[0] > q.shape[0] or d.shape[1] > Hkv):
+        raise ValueError(f"kvcache_attention: {name} {tuple(d.shape)} does not broadcast to [{q.shape[0]}, {Hkv}]")
+    return d
+
+
 def kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor] = None,
                       v: Optional[torch.Tensor] = None, cache_seqlens=None, block_table: Optional[torch.Tensor] = None,
                       softmax_scale: Optional[float] = None, causal: bool = False, num_splits: int = 0,
-                      return_softmax_lse: bool = False, **unsupported):
+                      return_softmax_lse: bool = False, k_descale=None, v_descale=None, **unsupported):
     """flash_attn_with_kvcache on the MFMA kernels: softmax(q k^T scale [bottom-right causal]) v over each sequence's cached keys,
     after appending k / v into the cache in place.  Returns O [B, Sq, H, D] in q's dtype, or (O, LSE [B, H, Sq] fp32) with
     return_softmax_lse.  cache_seqlens: an int (broadcast to every sequence) or a device int32 [B]; None = the whole capacity.
+    k_cache / v_cache both torch.float8_e4m3fn: k_descale / v_descale (a float, or a device fp32 tensor that broadcasts to [B, H_kv];
+    default 1.0) give the value of a byte, e4m3fn(byte) * descale[b, h_kv], and k / v are quantised into the cache; with a 16-bit cache
+    they must stay None.
     rotary_cos / rotary_sin / cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes are accepted at their defaults only.
     Raises ValueError outside the kernels' scope (see the module docstring)."""
     for name, val in unsupported.items():
@@ -136,8 +198,21 @@ def kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
             cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
     if not isinstance(cache_seqlens, torch.Tensor):
         raise ValueError("kvcache_attention: cache_seqlens must be an int, or a device int32 [batch] tensor")
-    _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table)
+    fp8 = any(isinstance(t, torch.Tensor) and t.dtype == torch.float8_e4m3fn for t in (k_cache, v_cache))
+    if not fp8 and (k_descale is not None or v_descale is not None):
+        raise ValueError("kvcache_attention: k_descale / v_descale go with float8_e4m3fn caches only")
+    _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table, fp8)
     sm = float(softmax_scale) if softmax_scale is not None else float(q.shape[-1]) ** -0.5
+    if fp8:
+        kd, vd = (_descale(d, q, k_cache.shape[2], n) for d, n in ((k_descale, "k_descale"), (v_descale, "v_descale")))
+        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)  # (the ops take the bytes: kvcache_fp8_forward)
+        if k is not None and k.shape[1] > 0:
+            out, lse = torch.ops.umfa.kvcache_fp8_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, kd, vd, block_table, bool(causal),
+                                                                 sm, int(num_splits))
+        else:
+            out, lse = torch.ops.umfa.kvcache_fp8_forward(q, k_cache, v_cache, cache_seqlens, kd, vd, block_table, bool(causal), sm,
+                                                          int(num_splits))
+        return (out, lse) if return_softmax_lse else out
     if k is not None and k.shape[1] > 0:
         out, lse = torch.ops.umfa.kvcache_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, block_table, bool(causal), sm,
                                                          int(num_splits))

@@ -573,14 +573,8 @@ def varlen_attention_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q
     return dq, dk, dv
 
 
-def kvcache_attention_forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_new=None, *, scale: float,
-                              causal: bool = False, num_splits: int = 0, out_dtype=None):
-    """O [B, Sq, H, D] and LSE [B, H, Sq] (fp32, natural log) of attention over a paged or static KV cache
-    (umfa_kvcache_attention_forward_stream), appending k_new / v_new [B, S_new, H_kv, D] into the cache in place first.
-    q [B, Sq, H, D]; paged: k_cache / v_cache [num_pages, page_size, H_kv, D] with block_table device int32 [B, max_pages]; static
-    (block_table None): k_cache / v_cache [B, S_max, H_kv, D] -- HF's [B, H_kv, S_max, D] as its .transpose(1, 2) view, no copy.
-    cache_seqlens device int32 [B].  fp16 / bf16 with a contiguous head_dim and strides that are multiples of 8 elements.  Asynchronous
-    on torch's current stream; cache_seqlens and block_table are never read back."""
+def _kvcache_forward(entry, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype):
+    """the call both KV-cache entries share; extra: the arguments behind num_splits (the fp8 entry's descales)"""
     B, Sq, H, D = q.shape
     if B > 1 and (cache_seqlens.stride(0) != 1 or (block_table is not None and block_table.stride(1) != 1)):
         raise ValueError("kvcache_attention_forward: cache_seqlens and the rows of block_table must be contiguous")
@@ -596,9 +590,49 @@ def kvcache_attention_forward(q, k_cache, v_cache, cache_seqlens, block_table=No
     new = [None, None, None, None]
     if Snew:
         new = [ctypes.c_void_p(k_new.data_ptr()), _i64(k_new.stride()[:3]), ctypes.c_void_p(v_new.data_ptr()), _i64(v_new.stride()[:3])]
-    _check_error(_lib.umfa_kvcache_attention_forward_stream(
+    _check_error(entry(
         context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:3]), ctypes.c_void_p(k_cache.data_ptr()),
         _i64(k_cache.stride()[:3]), ctypes.c_void_p(v_cache.data_ptr()), _i64(v_cache.stride()[:3]), *new, bt, int(bt_stride),
         ctypes.c_void_p(cache_seqlens.data_ptr()), B, Sq, Snew, H, Hkv, D, int(page_size), int(num_pages), int(max_pages), float(scale),
-        bool(causal), _PREC[q.dtype], ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()), int(num_splits)))
+        bool(causal), _PREC[q.dtype], ctypes.c_void_p(out.data_ptr()), _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()), int(num_splits),
+        *extra))
     return out, lse
+
+
+def kvcache_attention_forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_new=None, *, scale: float,
+                              causal: bool = False, num_splits: int = 0, out_dtype=None):
+    """O [B, Sq, H, D] and LSE [B, H, Sq] (fp32, natural log) of attention over a paged or static KV cache
+    (umfa_kvcache_attention_forward_stream), appending k_new / v_new [B, S_new, H_kv, D] into the cache in place first.
+    q [B, Sq, H, D]; paged: k_cache / v_cache [num_pages, page_size, H_kv, D] with block_table device int32 [B, max_pages]; static
+    (block_table None): k_cache / v_cache [B, S_max, H_kv, D] -- HF's [B, H_kv, S_max, D] as its .transpose(1, 2) view, no copy.
+    cache_seqlens device int32 [B].  fp16 / bf16 with a contiguous head_dim and strides that are multiples of 8 elements.  Asynchronous
+    on torch's current stream; cache_seqlens and block_table are never read back."""
+    return _kvcache_forward(_lib.umfa_kvcache_attention_forward_stream, (), q, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                            scale, causal, num_splits, out_dtype)
+
+
+def _descale_arg(d, B, Hkv, name):
+    """(pointer, (batch, head) element strides) of a device fp32 descale that broadcasts to [B, H_kv]; nothing is read or copied"""
+    if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or not d.is_cuda or d.dim() > 2:
+        raise ValueError(f"kvcache_attention_fp8_forward: {name} must be a device fp32 tensor that broadcasts to [batch, num_kv_heads]")
+    try:
+        e = d.expand(B, Hkv)
+    except RuntimeError:
+        raise ValueError(f"kvcache_attention_fp8_forward: {name} {tuple(d.shape)} does not broadcast to [{B}, {Hkv}]") from None
+    return ctypes.c_void_p(e.data_ptr()), _i64(e.stride())
+
+
+def kvcache_attention_fp8_forward(q, k_cache, v_cache, cache_seqlens, k_descale, v_descale, block_table=None, k_new=None, v_new=None, *,
+                                  scale: float, causal: bool = False, num_splits: int = 0, out_dtype=None):
+    """kvcache_attention_forward over an fp8 cache (umfa_kvcache_attention_fp8_forward_stream): k_cache / v_cache torch.float8_e4m3fn in
+    the same layouts, q / k_new / v_new fp16 or bf16.  k_descale / v_descale: device fp32, a scalar, [H_kv], [B, 1] or [B, H_kv]; a cache
+    byte stands for e4m3fn(byte) * descale[b, h_kv], and k_new / v_new are stored as e4m3fn(clamp(x / descale, -448, 448)).  Cache strides
+    multiples of 16 with a contiguous head_dim.  The descales are never read back."""
+    if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"kvcache_attention_fp8_forward: k_cache and v_cache must both be torch.float8_e4m3fn (got {k_cache.dtype}, {v_cache.dtype})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"kvcache_attention_fp8_forward: q must be fp16 or bf16 (got {q.dtype})")
+    B, Hkv = q.shape[0], k_cache.shape[2]
+    extra = (*_descale_arg(k_descale, B, Hkv, "k_descale"), *_descale_arg(v_descale, B, Hkv, "v_descale"))
+    return _kvcache_forward(_lib.umfa_kvcache_attention_fp8_forward_stream, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new,
+                            v_new, scale, causal, num_splits, out_dtype)
