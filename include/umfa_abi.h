@@ -547,6 +547,51 @@ mfa_error_t umfa_kvcache_attention_fp8_forward_stream(mfa_context_t context, voi
                                                       int32_t num_splits, const float* k_descale, const int64_t* k_descale_strides,
                                                       const float* v_descale, const int64_t* v_descale_strides);
 
+/* MI355X extra: PACKED variable-length queries over the paged or static KV cache of umfa_kvcache_attention_forward_stream
+ * (flash-attention's flash_attn_varlen_func(..., block_table=...): continuous batching, chunked prefill beside decode), forward only.
+ *   q [total_q, num_heads, D]; q_strides = {token, head} in ELEMENTS (NULL: dense), head_dim contiguous -- a slice of a fused QKV
+ *   projection goes in without a copy.  cu_seqlens_q DEVICE int32 [batch + 1]: sequence b owns rows cu[b] .. cu[b+1] - 1,
+ *   L_q,b = cu[b+1] - cu[b]; max_seqlen_q is a host bound on L_q,b (<= total_q).  k_cache, v_cache, their strides, block_table,
+ *   block_table_stride, cache_seqlens, page_size, num_pages, max_pages_per_seq and the static form (block_table == NULL) are exactly
+ *   umfa_kvcache_attention_forward_stream's.
+ *   Append (has_new): k_new / v_new [total_q, num_kv_heads, D] ({token, head} strides), packed by the SAME cu_seqlens_q; sequence b's
+ *   rows are written into the cache in place at positions cache_seqlens[b] .. on `stream` before the attention, and
+ *   L_k,b = min(L0_b + L_q,b, cap); without, L_k,b = L0_b.  L0_b is cache_seqlens[b] clamped into [0, cap],
+ *   cap = max_pages_per_seq * page_size (static: S_max).  cache_seqlens is not modified.
+ *   Causal is BOTTOM-RIGHT aligned per sequence: query i of sequence b sees key j iff j <= i + L_k,b - L_q,b and j's page entry lies in
+ *   [0, num_pages); non-causal sees every such key below L_k,b.  A row that sees no key gives O = 0 exactly and LSE = -inf.  Rows of
+ *   out / lse that no sequence covers are not written.
+ *   Memory safety, on the device, for any contents of cu_seqlens_q, cache_seqlens and the block table: cu values are clamped into
+ *   [0, total_q] and L_q,b to max_seqlen_q; lengths and table entries are treated as in umfa_kvcache_attention_forward_stream; append
+ *   rows past the capacity or into a page the table does not hold are dropped.  Results are DEFINED only for non-decreasing cu with
+ *   cu[batch] <= total_q; for anything else the only promise is that nothing outside q, the pools, k_new / v_new, out, lse and the
+ *   library's own scratch is touched.
+ *   Work follows the rows that exist: a sequence with (num_heads / num_kv_heads) * L_q,b <= 32 is one work item per KV head in the decode
+ *   form, any other ceil(that / 128) items of 128 rows, both in one launch; a pre-pass launch writes the item list (at most
+ *   num_kv_heads * min(floor(g total_q / 128) + batch, batch * ceil(g max_seqlen_q / 128)) entries) into the stream's pooled workspace.
+ *   num_splits: 0 = the library picks the split-KV parts from that bound, the CU count and the capacity; > 0 forces that many for every
+ *   item.  The list and the split partials come from the stream's pooled workspace: valid under stream capture after a warm-up call, a
+ *   capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION.  Never synchronises; a captured graph follows the contents
+ *   of cu_seqlens_q, cache_seqlens and block_table on replay (total_q, batch and max_seqlen_q are the capture's).
+ *   Host-known values: total_q, batch, max_seqlen_q, the head counts, D, the page geometry, num_splits, has_new -- nothing else.
+ *   Scope: fp16 / bf16 caches, head_dim 64 / 128, softmax_scale > 0; else MFA_ERROR_INVALID_ARGS -- no fall-back.
+ * out dense [total_q, num_heads, D] in out_precision (fp32 or the input type); lse (optional) fp32 [num_heads, total_q], natural log. */
+mfa_error_t umfa_varlen_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                         void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                         const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                         const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                         int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+                                                         uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new,
+                                                         uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
+                                                         uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                         int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                         int32_t num_splits);
+
+/* Debug: how many work items the last umfa_varlen_kvcache_attention_forward_stream call on `stream` ran in the decode form and in the
+ * 128-row form (counted by the forward kernel itself).  Valid while nothing else has used the stream's pooled workspace since that
+ * call; SYNCHRONISES the stream.  MFA_ERROR_INVALID_ARGS when the stream has no workspace yet. */
+mfa_error_t umfa_varlen_kvcache_item_counts(mfa_context_t context, void* stream, uint32_t* decode_items, uint32_t* block_items);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

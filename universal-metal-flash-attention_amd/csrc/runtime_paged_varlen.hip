@@ -1,0 +1,143 @@
+// runtime_paged_varlen.hip -- the C ABI of packed variable-length queries over a paged / static KV cache (include/umfa_abi.h):
+// umfa_varlen_kvcache_attention_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
+// the device, so a captured graph follows their contents on replay.  Launch order on the stream: the packed append of k_new / v_new
+// (when given), the item-list pre-pass, the attention, and with split-KV the fold.  The item list and the split partials come from the
+// stream's pooled workspace (a capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION: warm up first).  Anything
+// outside the kernels' scope is MFA_ERROR_INVALID_ARGS: no silent fall-back.
+#include <string.h>
+
+#include "runtime_internal.h"
+#include "fa_paged_varlen.h"
+
+using namespace umfa;
+using namespace umfa_rt;
+
+namespace {
+
+mfa_error_t rc_pv(hipError_t e) {
+    return e == hipSuccess ? MFA_SUCCESS : e == hipErrorInvalidValue ? MFA_ERROR_INVALID_ARGS
+                                         : e == hipErrorOutOfMemory ? MFA_ERROR_MEMORY_ALLOCATION : MFA_ERROR_EXECUTION_FAILED;
+}
+
+int pv_cu_count(int dev) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        n = 256;
+    }
+    return n;
+}
+
+// split-KV parts when the caller leaves it to the library: kvcache_attention's rule (runtime_paged.hip) on the item bound -- enough
+// workgroups for every CU's slots (one per CU at head_dim 128, two at 64), each part at least two 128-key steps of the capacity, at
+// most 64 parts.  With every L_q equal the bound is the existing entry's item count, so both entries choose the same.
+uint32_t pv_auto_splits(const PagedVarlenParams& v, int ncu) {
+    const uint64_t items = v.n_items;
+    const uint64_t slots = (uint64_t)ncu * (v.p.D == 128 ? 1 : 2);
+    if (items == 0 || items >= slots) return 1;
+    uint64_t n = (slots + items - 1) / items;
+    const uint64_t steps = ((uint64_t)v.p.max_pages * v.p.page_size + 127) / 128;
+    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
+    n = n < by_len ? n : by_len;
+    return (uint32_t)(n < 64 ? n : 64);
+}
+
+constexpr size_t PV_HDR_B = 256;  // the tally's words at the front of the workspace block
+
+}  // namespace
+
+mfa_error_t umfa_varlen_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                         void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                         const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                         const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                         int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+                                                         uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new,
+                                                         uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
+                                                         uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                         int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                         int32_t num_splits) {
+    Context* ctx = as_ctx(context);
+    if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !cu_seqlens_q || !k_cache_strides || !v_cache_strides)
+        return MFA_ERROR_INVALID_ARGS;
+    if (input_precision != MFA_PRECISION_FP16 && input_precision != MFA_PRECISION_BF16) return MFA_ERROR_INVALID_ARGS;
+    if (out_precision != MFA_PRECISION_FP32 && out_precision != input_precision) return MFA_ERROR_INVALID_ARGS;
+    if (!(softmax_scale > 0.0f) || ((uintptr_t)cache_seqlens & 3) || ((uintptr_t)block_table & 3) || ((uintptr_t)cu_seqlens_q & 3) || num_splits < 0)
+        return MFA_ERROR_INVALID_ARGS;
+    if (has_new && (!k_new || !v_new || !k_new_strides || !v_new_strides)) return MFA_ERROR_INVALID_ARGS;
+    if (block_table && block_table_stride < (int64_t)max_pages_per_seq) return MFA_ERROR_INVALID_ARGS;
+    if (max_seqlen_q > total_q) return MFA_ERROR_INVALID_ARGS;
+    PagedVarlenParams v;
+    memset(&v, 0, sizeof(v));
+    PagedParams& p = v.p;
+    p.q = q; p.kc = k_cache; p.vc = v_cache; p.bt = block_table; p.seqlens = cache_seqlens;
+    p.out = out; p.lse = lse;
+    v.cu = cu_seqlens_q; v.Tq = total_q;
+    p.B = batch; p.Sq = max_seqlen_q; p.Snew = has_new ? 1 : 0; p.H = num_heads; p.Hkv = num_kv_heads; p.D = head_dim;
+    p.page_size = page_size;
+    // static cache: page b is sequence b's row of S_max = page_size tokens
+    p.num_pages = block_table ? num_pages : batch;
+    p.max_pages = block_table ? max_pages_per_seq : 1;
+    p.bt_stride = block_table ? block_table_stride : 0;
+    p.page_shift = (page_size && !(page_size & (page_size - 1))) ? __builtin_ctz(page_size) : -1;
+    p.qst = q_strides ? q_strides[0] : (int64_t)num_heads * head_dim;
+    p.qsh = q_strides ? q_strides[1] : (int64_t)head_dim;
+    p.kpg = k_cache_strides[0]; p.kst = k_cache_strides[1]; p.ksh = k_cache_strides[2];
+    p.vpg = v_cache_strides[0]; p.vst = v_cache_strides[1]; p.vsh = v_cache_strides[2];
+    if (has_new) {
+        p.kn = k_new; p.vn = v_new;
+        p.knt = k_new_strides[0]; p.knh = k_new_strides[1];
+        p.vnt = v_new_strides[0]; p.vnh = v_new_strides[1];
+    }
+    p.scale = softmax_scale;
+    p.causal = causal ? 1 : 0;
+    p.in_prec = dense_prec(input_precision);
+    p.out_prec = dense_prec(out_precision);
+    if (num_kv_heads == 0 || num_heads % num_kv_heads) return MFA_ERROR_INVALID_ARGS;
+    p.nsplit = 1;
+    v.n_items = paged_varlen_item_bound(v);
+    if (!paged_varlen_supported(v) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
+    const char* name = "none";
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const int dev = stream_device((hipStream_t)stream);
+    DeviceGuard guard(dev);
+    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : pv_auto_splits(v, pv_cu_count(dev));
+    if (!paged_varlen_supported(v)) return MFA_ERROR_INVALID_ARGS;
+    if (v.n_items) {
+        // one block of the pooled workspace: the form tally (PV_HDR_B bytes), the item list, then (split) the partials
+        StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
+        const size_t list_b = ((size_t)v.n_items * 2 * sizeof(int32_t) + 255) & ~(size_t)255;
+        const size_t part_b = p.nsplit > 1 ? (size_t)p.nsplit * total_q * num_heads * (p.D + 2) * sizeof(float) : 0;
+        char* const ws = (char*)sc.workspace.ensure(PV_HDR_B + list_b + part_b, (hipStream_t)stream);
+        if (!ws) return MFA_ERROR_MEMORY_ALLOCATION;
+        v.counts = (uint32_t*)ws;
+        v.items = (int32_t*)(ws + PV_HDR_B);
+        if (part_b) p.part = (float*)(ws + PV_HDR_B + list_b);
+    }
+    if (has_new) {
+        if (const hipError_t e = launch_paged_varlen_append(v, (hipStream_t)stream); e != hipSuccess) return rc_pv(e);
+    }
+    const hipError_t e = launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
+    ctx->last_kernel = name;
+    return rc_pv(e);
+}
+
+// debug: the tally of the last umfa_varlen_kvcache_attention_forward_stream call on `stream` (nothing else may have used the stream's
+// workspace since).  Synchronises the stream.
+mfa_error_t umfa_varlen_kvcache_item_counts(mfa_context_t context, void* stream, uint32_t* decode_items, uint32_t* block_items) {
+    Context* ctx = as_ctx(context);
+    if (!ctx || !decode_items || !block_items) return MFA_ERROR_INVALID_ARGS;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const int dev = stream_device((hipStream_t)stream);
+    DeviceGuard guard(dev);
+    StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
+    if (!sc.workspace.ptr || sc.workspace.bytes < PV_HDR_B) return MFA_ERROR_INVALID_ARGS;
+    uint32_t host[2] = {0, 0};
+    if (hipMemcpyAsync(host, sc.workspace.ptr, sizeof(host), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return MFA_ERROR_EXECUTION_FAILED;
+    }
+    *decode_items = host[0];
+    *block_items = host[1];
+    return MFA_SUCCESS;
+}

@@ -636,3 +636,48 @@ def kvcache_attention_fp8_forward(q, k_cache, v_cache, cache_seqlens, k_descale,
     extra = (*_descale_arg(k_descale, B, Hkv, "k_descale"), *_descale_arg(v_descale, B, Hkv, "v_descale"))
     return _kvcache_forward(_lib.umfa_kvcache_attention_fp8_forward_stream, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new,
                             v_new, scale, causal, num_splits, out_dtype)
+
+
+def varlen_kvcache_attention_forward(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, block_table=None, k_new=None,
+                                     v_new=None, *, scale: float, causal: bool = False, num_splits: int = 0, out_dtype=None):
+    """O [T_q, H, D] and LSE [H, T_q] (fp32, natural log) of packed variable-length queries over a paged or static KV cache
+    (umfa_varlen_kvcache_attention_forward_stream), appending k_new / v_new [T_q, H_kv, D] (packed by the same cu_seqlens_q) into the
+    cache in place first.  q [T_q, H, D] with a contiguous head_dim and token / head strides that are multiples of 8 elements;
+    cu_seqlens_q device int32 [B + 1]; max_seqlen_q a host int; the caches, block_table and cache_seqlens as kvcache_attention_forward
+    takes them.  Asynchronous on torch's current stream; cu_seqlens_q, cache_seqlens and block_table are never read back."""
+    Tq, H, D = q.shape
+    B = cu_seqlens_q.numel() - 1
+    if cu_seqlens_q.dim() != 1 or B < 1 or cache_seqlens.shape != (B,) or cu_seqlens_q.stride(0) != 1 or (B > 1 and cache_seqlens.stride(0) != 1) \
+            or (block_table is not None and (block_table.shape[0] != B or block_table.stride(1) != 1)):
+        raise ValueError("varlen_kvcache_attention_forward: cu_seqlens_q [B + 1], cache_seqlens [B] and the rows of block_table [B, .] "
+                         "must be contiguous")
+    num_pages, page_size, Hkv = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    if block_table is not None:
+        max_pages, bt_stride, bt = block_table.shape[1], block_table.stride(0), ctypes.c_void_p(block_table.data_ptr())
+    else:
+        max_pages, bt_stride, bt = 1, 0, None
+    has_new = k_new is not None
+    out = torch.empty((Tq, H, D), dtype=out_dtype or q.dtype, device=q.device)
+    lse = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    new = [None, None, None, None]
+    if has_new:
+        if k_new.shape != (Tq, Hkv, D) or v_new.shape != (Tq, Hkv, D):
+            raise ValueError(f"varlen_kvcache_attention_forward: k_new / v_new must be [T_q, H_kv, D] = {(Tq, Hkv, D)}")
+        new = [ctypes.c_void_p(k_new.data_ptr()), _i64(k_new.stride()[:2]), ctypes.c_void_p(v_new.data_ptr()), _i64(v_new.stride()[:2])]
+    _check_error(_lib.umfa_varlen_kvcache_attention_forward_stream(
+        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]), ctypes.c_void_p(k_cache.data_ptr()),
+        _i64(k_cache.stride()[:3]), ctypes.c_void_p(v_cache.data_ptr()), _i64(v_cache.stride()[:3]), *new, bt, int(bt_stride),
+        ctypes.c_void_p(cache_seqlens.data_ptr()), Tq, B, int(max_seqlen_q), ctypes.c_void_p(cu_seqlens_q.data_ptr()), bool(has_new), H, Hkv, D,
+        int(page_size), int(num_pages), int(max_pages), float(scale), bool(causal), _PREC[q.dtype], ctypes.c_void_p(out.data_ptr()),
+        _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()), int(num_splits)))
+    return out, lse
+
+
+def varlen_kvcache_item_counts(device=None):
+    """(decode-form items, 128-row items) the last varlen_kvcache_attention_forward on torch's current stream ran, counted by the
+    kernel (umfa_varlen_kvcache_item_counts).  Debug: synchronises the stream."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check_error(_lib.umfa_varlen_kvcache_item_counts(context(), ctypes.c_void_p(stream), ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value

@@ -1,0 +1,151 @@
+"""Packed variable-length queries over a paged or static KV cache, on the 16-bit MFMA kernels: the `umfa::varlen_kvcache_forward`
+custom op (and its appending form `umfa::varlen_kvcache_forward_append`, which declares the in-place write of k_cache / v_cache so that
+torch.compile orders it), both with fake implementations, and `varlen_kvcache_attention`, the call an inference server with
+continuous batching and chunked prefill makes (flash-attention's flash_attn_varlen_func(..., block_table=...)).
+
+Layout: q [T_q, H, D], packed; cu_seqlens_q device int32 [B + 1] (sequence b owns rows cu[b] .. cu[b+1] - 1); max_seqlen_q a host int.
+k_cache / v_cache, block_table and cache_seqlens as `kvcache_attention` takes them (paged [num_pages, page_size, H_kv, D] with
+block_table int32 [B, max_pages_per_seq], or static [B, S_max, H_kv, D] with block_table None).  k / v [T_q, H_kv, D], packed by the
+same cu_seqlens_q, are written into the cache at cache_seqlens[b] .. before the attention, which then covers cache_seqlens[b] + L_q,b
+keys; cache_seqlens itself is not advanced.  Causal is bottom-right aligned per sequence.  One launch serves prefill chunks (128-row work
+items) and decode / speculative sequences (the decode form) together; work follows the rows that exist.  cu_seqlens_q, cache_seqlens and
+the table stay on the device: no call synchronises, and a captured graph follows their contents on replay.  Lengths, cu values and table
+entries outside their ranges are clamped / masked on the device.
+
+Scope: fp16 / bf16 device tensors, head_dim 64 / 128, forward only (a backward through these ops raises).  Anything else raises
+ValueError: there is no fall-back.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import ops
+from .kvcache import KVCACHE_HEAD_DIMS, _DTYPES, _strides_ok
+
+
+def _packed_view(t: torch.Tensor) -> torch.Tensor:
+    """t itself when the kernels can read it (contiguous head_dim, token / head strides multiples of 8, 16-byte aligned), else a copy"""
+    return t if _strides_ok(t) else t.contiguous()
+
+
+@torch.library.custom_op("umfa::varlen_kvcache_forward", mutates_args=(), device_types="cuda")
+def varlen_kvcache_forward(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                           cache_seqlens: torch.Tensor, block_table: Optional[torch.Tensor], causal: bool, scale: float,
+                           num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """O [T_q, H, D] (q's dtype) and the fp32 log-sum-exp [H, T_q] (umfa_varlen_kvcache_attention_forward_stream)."""
+    return ops.varlen_kvcache_attention_forward(_packed_view(q), k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), cache_seqlens, block_table,
+                                                scale=float(scale), causal=bool(causal), num_splits=int(num_splits))
+
+
+@varlen_kvcache_forward.register_fake
+def _(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, num_splits):
+    Tq, H, D = q.shape
+    return q.new_empty((Tq, H, D)), q.new_empty((H, Tq), dtype=torch.float32)
+
+
+@torch.library.custom_op("umfa::varlen_kvcache_forward_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def varlen_kvcache_forward_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                                  cu_seqlens_q: torch.Tensor, max_seqlen_q: int, cache_seqlens: torch.Tensor,
+                                  block_table: Optional[torch.Tensor], causal: bool, scale: float,
+                                  num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """varlen_kvcache_forward after writing k / v [T_q, H_kv, D] into k_cache / v_cache in place at cache_seqlens[b] .."""
+    return ops.varlen_kvcache_attention_forward(_packed_view(q), k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), cache_seqlens, block_table,
+                                                _packed_view(k), _packed_view(v), scale=float(scale), causal=bool(causal),
+                                                num_splits=int(num_splits))
+
+
+@varlen_kvcache_forward_append.register_fake
+def _(q, k_cache, v_cache, k, v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, causal, scale, num_splits):
+    Tq, H, D = q.shape
+    return q.new_empty((Tq, H, D)), q.new_empty((H, Tq), dtype=torch.float32)
+
+
+# flash_attn_varlen_func / flash_attn_with_kvcache arguments this entry accepts only at their defaults
+_UNSUPPORTED = {"rotary_cos": None, "rotary_sin": None, "cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
+                "softcap": 0.0, "alibi_slopes": None, "seqused_k": None, "dropout_p": 0.0}
+
+
+def _check(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v):
+    def bad(msg):
+        raise ValueError(f"varlen_kvcache_attention: {msg}")
+
+    if not isinstance(q, torch.Tensor) or q.dim() != 3 or not q.is_cuda or q.dtype not in _DTYPES:
+        bad(f"q must be a packed 3-D [T_q, H, D] fp16 / bf16 device tensor (got {getattr(q, 'shape', q)}, {getattr(q, 'dtype', None)})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or not t.is_cuda or t.dtype not in _DTYPES:
+            bad(f"{name} must be a 4-D fp16 / bf16 device tensor (got {getattr(t, 'shape', t)}, {getattr(t, 'dtype', None)}); fp8 caches are "
+                "served by kvcache_attention only")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or k_cache.shape != v_cache.shape or k_cache.device != q.device \
+            or v_cache.device != q.device:
+        bad("k_cache and v_cache must match each other in shape and q in dtype and device")
+    Tq, H, D = q.shape
+    Hkv = k_cache.shape[2]
+    if D not in KVCACHE_HEAD_DIMS or k_cache.shape[3] != D:
+        bad(f"head_dim must be 64 or 128 and equal in q and the cache (got {D}, {k_cache.shape[3]})")
+    if Hkv == 0 or H % Hkv:
+        bad(f"num_heads ({H}) must be a multiple of the cache's num_kv_heads ({Hkv})")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not _strides_ok(t) or t.stride(1) < D:
+            bad(f"{name} needs a contiguous head_dim, page / token / head strides that are multiples of 16 bytes and a 16-byte aligned base")
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 \
+            or cu_seqlens_q.device != q.device:
+        bad("cu_seqlens_q must be a device int32 [batch + 1] tensor")
+    if cu_seqlens_q.stride(0) != 1:
+        bad(f"cu_seqlens_q must be contiguous (got stride {cu_seqlens_q.stride(0)})")
+    B = cu_seqlens_q.numel() - 1
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or max_seqlen_q > Tq:
+        bad(f"max_seqlen_q must be a host int in [0, T_q = {Tq}] (got {max_seqlen_q!r})")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B \
+                or block_table.device != q.device or block_table.stride(1) != 1 or (B > 1 and block_table.stride(0) < block_table.shape[1]):
+            bad("block_table must be a device int32 [batch, max_pages_per_seq] tensor with unit column stride and rows that do not overlap")
+        if k_cache.shape[1] % 16:
+            bad(f"a paged cache's page_size must be a multiple of 16 (got {k_cache.shape[1]})")
+    elif k_cache.shape[0] < B:
+        bad(f"a static cache needs one row per sequence ({k_cache.shape[0]} rows for batch {B})")
+    if (k is None) != (v is None):
+        bad("k and v must be given together")
+    if k is not None:
+        for name, t in (("k", k), ("v", v)):
+            if not isinstance(t, torch.Tensor) or t.shape != (Tq, Hkv, D) or t.dtype != q.dtype or t.device != q.device:
+                bad(f"{name} must be [T_q, num_kv_heads, head_dim] = {(Tq, Hkv, D)} in q's dtype on q's device, packed by cu_seqlens_q "
+                    f"(got {tuple(getattr(t, 'shape', ()))})")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,) \
+            or cache_seqlens.device != q.device:
+        bad("cache_seqlens must be a device int32 [batch] tensor")
+    # the kernels read cache_seqlens[b] at element b: an expanded (stride 0) or strided view would hand every sequence a wrong length
+    if B > 1 and cache_seqlens.stride(0) != 1:
+        bad(f"cache_seqlens must be contiguous (got stride {cache_seqlens.stride(0)}): pass cache_seqlens.contiguous()")
+
+
+def varlen_kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
+                             cache_seqlens: torch.Tensor, block_table: Optional[torch.Tensor] = None, k: Optional[torch.Tensor] = None,
+                             v: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, causal: bool = False,
+                             num_splits: int = 0, return_softmax_lse: bool = False, **unsupported):
+    """softmax(q k^T scale [bottom-right causal]) v for packed queries q [T_q, H, D] (sequence b = rows cu_seqlens_q[b] ..
+    cu_seqlens_q[b+1] - 1) over each sequence's cached keys, after appending the packed k / v [T_q, H_kv, D] into the cache in place.
+    Returns O [T_q, H, D] in q's dtype, or (O, LSE [H, T_q] fp32) with return_softmax_lse.  Rows no sequence covers are left unwritten.
+    rotary_cos / rotary_sin / cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes / seqused_k / dropout_p are accepted
+    at their defaults only.  Raises ValueError outside the kernels' scope (see the module docstring)."""
+    for name, val in unsupported.items():
+        if name not in _UNSUPPORTED and name != "rotary_interleaved":
+            raise TypeError(f"varlen_kvcache_attention() got an unexpected keyword argument '{name}'")
+        if name == "rotary_interleaved":
+            continue  # (only meaningful with rotary_cos, which is refused below)
+        default = _UNSUPPORTED[name]
+        same = val is None if default is None else (tuple(val) == default if name == "window_size" else val == default)
+        if not same:
+            raise ValueError(f"varlen_kvcache_attention: {name} is not supported (only its default, {default!r}, is accepted)")
+    _check(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v)
+    sm = float(softmax_scale) if softmax_scale is not None else float(q.shape[-1]) ** -0.5
+    if not sm > 0.0:
+        raise ValueError(f"varlen_kvcache_attention: softmax_scale must be positive (got {softmax_scale})")
+    if k is not None:
+        out, lse = torch.ops.umfa.varlen_kvcache_forward_append(q, k_cache, v_cache, k, v, cu_seqlens_q, int(max_seqlen_q), cache_seqlens,
+                                                                block_table, bool(causal), sm, int(num_splits))
+    else:
+        out, lse = torch.ops.umfa.varlen_kvcache_forward(q, k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), cache_seqlens, block_table,
+                                                         bool(causal), sm, int(num_splits))
+    return (out, lse) if return_softmax_lse else out
