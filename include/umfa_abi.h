@@ -592,6 +592,57 @@ mfa_error_t umfa_varlen_kvcache_attention_forward_stream(mfa_context_t context, 
  * call; SYNCHRONISES the stream.  MFA_ERROR_INVALID_ARGS when the stream has no workspace yet. */
 mfa_error_t umfa_varlen_kvcache_item_counts(mfa_context_t context, void* stream, uint32_t* decode_items, uint32_t* block_items);
 
+/* MI355X extra: umfa_kvcache_attention_forward_stream / umfa_kvcache_attention_fp8_forward_stream with the rotary embedding of q and
+ * k_new fused in (flash_attn_with_kvcache's rotary_cos / rotary_sin / rotary_interleaved).  ONE pre-pass launch replaces the append
+ * launch: it rotates k_new into the cache, appends v_new unrotated and rotates q into a dense operand-type image in the stream's pooled
+ * workspace; the unchanged attention kernel then reads that image.  A rotary call launches as many kernels as the same call without.
+ *   cache_fp8: false = 16-bit caches (umfa_kvcache_attention_forward_stream's arguments; the four descale arguments must be NULL);
+ *   true = e4m3fn caches (umfa_kvcache_attention_fp8_forward_stream's arguments).  seqlen_new must be > 0 (rotary needs new tokens).
+ *   rotary_cos / rotary_sin: DEVICE tables [seqlen_ro, rotary_dim / 2] in rotary_table_precision (fp32, or input_precision: 16-bit
+ *   entries convert exactly to fp32 on load), unit column stride, rotary_row_stride ELEMENTS between rows (>= rotary_dim / 2), bases and
+ *   rows 16-byte aligned.  rotary_dim: a multiple of 16 in [16, head_dim]; elements at rotary_dim and above pass through unchanged.
+ *   rotary_interleaved: element 2i pairs with 2i + 1; else (GPT-NeoX) element i pairs with i + rotary_dim / 2; table column i either way.
+ *   The pair (a, b) at column i and position pos becomes a' = fma(a, cos[pos, i], -(b sin[pos, i])), b' = fma(b, cos[pos, i],
+ *   a sin[pos, i]) in fp32, rounded once to the operand type; for an fp8 cache the rounded key is then quantised by the fp8 entry's rule.
+ *   Positions are read on the device: new-key row t of sequence b is rotated at L0_b + t, L0_b = cache_seqlens[b] clamped into [0, cap];
+ *   query row i at L0_b + i when causal, every query row at L0_b when not (flash-attention's rule).  A captured graph follows
+ *   cache_seqlens on replay.  A position >= seqlen_ro uses table row seqlen_ro - 1: memory-safe and defined, but meaningless -- the
+ *   caller sizes the table.
+ *   The result equals, in every bit of out, lse and both pools, the plain entry called on q and k_new rotated that way and rounded to
+ *   the operand type.  Every layout, clamp, masking, dropped-row and memory-safety rule, num_splits and the error codes are the plain
+ *   entries'.  The q image shares the pooled workspace with the split partials: valid under stream capture after a warm-up call, a
+ *   capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION and launches nothing.  Anything outside this scope:
+ *   MFA_ERROR_INVALID_ARGS -- no fall-back. */
+mfa_error_t umfa_kvcache_attention_rope_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                       void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                       const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                       const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                       int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                       uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                       uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                                       uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                       int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                       int32_t num_splits, bool cache_fp8, const float* k_descale,
+                                                       const int64_t* k_descale_strides, const float* v_descale,
+                                                       const int64_t* v_descale_strides, const void* rotary_cos, const void* rotary_sin,
+                                                       int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro,
+                                                       uint32_t rotary_dim, bool rotary_interleaved);
+
+/* MI355X extra: umfa_varlen_kvcache_attention_forward_stream with the same fused rotary embedding (16-bit caches; has_new must be true).
+ * Packed row t of sequence b (found on the device from cu_seqlens_q) is rotated at L0_b + (t - cu[b]) for the new keys and, when
+ * causal, for the queries; every query row of sequence b at L0_b when not causal.  Rows no sequence covers are neither appended nor
+ * used.  The q image [total_q, num_heads, D] shares the pooled workspace with the item list and the split partials.  Everything else:
+ * umfa_kvcache_attention_rope_forward_stream and umfa_varlen_kvcache_attention_forward_stream. */
+mfa_error_t umfa_varlen_kvcache_attention_rope_forward_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache, const int64_t* k_cache_strides,
+    void* v_cache, const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides, const void* v_new,
+    const int64_t* v_new_strides, const int32_t* block_table, int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+    uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads, uint32_t num_kv_heads,
+    uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+    int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const void* rotary_cos,
+    const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
+    bool rotary_interleaved);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

@@ -1,5 +1,6 @@
-// runtime_paged.hip -- the C ABI of KV-cache attention for inference (include/umfa_abi.h): umfa_kvcache_attention_forward_stream and, over an
-// fp8 (e4m3fn) cache with per-(batch, KV head) descales (fa_paged_fp8.h), umfa_kvcache_attention_fp8_forward_stream.
+// runtime_paged.hip -- the C ABI of KV-cache attention for inference (include/umfa_abi.h): umfa_kvcache_attention_forward_stream, over an
+// fp8 (e4m3fn) cache with per-(batch, KV head) descales (fa_paged_fp8.h) umfa_kvcache_attention_fp8_forward_stream, and with the rotary
+// embedding of q and k_new fused into the append launch (fa_paged_rope.h) umfa_kvcache_attention_rope_forward_stream.
 // In-stream, never synchronising: cache_seqlens and the block table stay on the device (the kernels read them when they run), so a
 // captured graph follows their contents on replay.  Launch order on the stream: the append of k_new / v_new (when given), the attention,
 // and with split-KV the fold.  Split partials come from the stream's pooled workspace (a capture that would have to grow it returns
@@ -8,6 +9,7 @@
 
 #include "runtime_internal.h"
 #include "fa_paged_fp8.h"
+#include "fa_paged_rope.h"
 
 using namespace umfa;
 using namespace umfa_rt;
@@ -50,15 +52,18 @@ uint32_t paged_auto_splits(const PagedParams& p, int ncu) {
 
 namespace {
 
-// both entries: fp8 = the cache is e4m3fn with the descales in f8 (cache strides in bytes), else 16-bit in input_precision
+// every entry: fp8 = the cache is e4m3fn with the descales in f8 (cache strides in bytes), else 16-bit in input_precision; rope != NULL:
+// the fused pre-pass (fa_paged_rope.h) stands in for the append and the attention reads its q image
 mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache,
                             const int64_t* k_cache_strides, void* v_cache, const int64_t* v_cache_strides, const void* k_new,
                             const int64_t* k_new_strides, const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
                             int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch, uint32_t seqlen_q,
                             uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
                             uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision,
-                            void* out, int32_t out_precision, float* lse, int32_t num_splits, bool fp8, PagedFp8Params f8) {
+                            void* out, int32_t out_precision, float* lse, int32_t num_splits, bool fp8, PagedFp8Params f8, const RopeArgs* rope = nullptr) {
     Context* ctx = as_ctx(context);
+    if (rope && (!seqlen_new || !rope->cos || !rope->sin || rope->table_f32 < 0))
+        return MFA_ERROR_INVALID_ARGS;
     if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !k_cache_strides || !v_cache_strides) return MFA_ERROR_INVALID_ARGS;
     if (input_precision != MFA_PRECISION_FP16 && input_precision != MFA_PRECISION_BF16) return MFA_ERROR_INVALID_ARGS;
     if (out_precision != MFA_PRECISION_FP32 && out_precision != input_precision) return MFA_ERROR_INVALID_ARGS;
@@ -104,6 +109,30 @@ mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, 
     DeviceGuard guard(dev);
     p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : paged_auto_splits(p, paged_cu_count(dev));
     if (!supported()) return MFA_ERROR_INVALID_ARGS;
+    if (rope) {
+        // one block of the pooled workspace: the rotated q image, then (split) the partials; every check and the allocation come before
+        // the first launch
+        PagedRopeParams r;
+        memset(&r, 0, sizeof(r));
+        r.v.p = p;
+        r.kd = f8.kd; r.vd = f8.vd; r.kdb = f8.kdb; r.kdh = f8.kdh; r.vdb = f8.vdb; r.vdh = f8.vdh;
+        paged_rope_fill(r, *rope);
+        r.fp8 = fp8 ? 1 : 0;
+        const size_t img_b = (paged_rope_qimg_bytes(r) + 255) & ~(size_t)255;
+        const size_t part_b = p.nsplit > 1 ? (size_t)p.nsplit * p.B * p.Hkv * p.R * (p.D + 2) * sizeof(float) : 0;
+        StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
+        char* const ws = (char*)sc.workspace.ensure(img_b + part_b ? img_b + part_b : 256, (hipStream_t)stream);
+        if (!ws) return MFA_ERROR_MEMORY_ALLOCATION;
+        r.qimg = ws;
+        if (part_b) p.part = (float*)(ws + img_b);
+        if (!paged_rope_supported(r)) return MFA_ERROR_INVALID_ARGS;
+        if (const hipError_t e = launch_paged_rope(r, (hipStream_t)stream); e != hipSuccess) return rc_paged(e);
+        p.q = r.qimg;
+        p.qsb = (int64_t)seqlen_q * num_heads * head_dim; p.qst = (int64_t)num_heads * head_dim; p.qsh = head_dim;
+        const hipError_t e = fp8 ? launch_fwd_16_paged_fp8(f8, (hipStream_t)stream, &name) : launch_fwd_16_paged(p, (hipStream_t)stream, &name);
+        ctx->last_kernel = name;
+        return rc_paged(e);
+    }
     if (p.nsplit > 1 && R) {
         StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
         const size_t bytes = (size_t)p.nsplit * p.B * p.Hkv * p.R * (p.D + 2) * sizeof(float);
@@ -156,4 +185,35 @@ mfa_error_t umfa_kvcache_attention_fp8_forward_stream(mfa_context_t context, voi
                            v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
                            num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
                            out_precision, lse, num_splits, true, f8);
+}
+
+mfa_error_t umfa_kvcache_attention_rope_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                       void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                       const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                       const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                       int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                       uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                       uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                                       uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                       int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                       int32_t num_splits, bool cache_fp8, const float* k_descale,
+                                                       const int64_t* k_descale_strides, const float* v_descale,
+                                                       const int64_t* v_descale_strides, const void* rotary_cos, const void* rotary_sin,
+                                                       int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro,
+                                                       uint32_t rotary_dim, bool rotary_interleaved) {
+    PagedFp8Params f8;
+    memset(&f8, 0, sizeof(f8));
+    if (cache_fp8) {
+        if (!k_descale || !v_descale || !k_descale_strides || !v_descale_strides) return MFA_ERROR_INVALID_ARGS;
+        f8.kd = k_descale; f8.kdb = k_descale_strides[0]; f8.kdh = k_descale_strides[1];
+        f8.vd = v_descale; f8.vdb = v_descale_strides[0]; f8.vdh = v_descale_strides[1];
+    } else if (k_descale || v_descale || k_descale_strides || v_descale_strides) {
+        return MFA_ERROR_INVALID_ARGS;
+    }
+    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
+    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,
+                           v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
+                           num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
+                           out_precision, lse, num_splits, cache_fp8, f8, &rope);
 }

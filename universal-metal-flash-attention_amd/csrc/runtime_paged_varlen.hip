@@ -1,5 +1,6 @@
 // runtime_paged_varlen.hip -- the C ABI of packed variable-length queries over a paged / static KV cache (include/umfa_abi.h):
-// umfa_varlen_kvcache_attention_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
+// umfa_varlen_kvcache_attention_forward_stream and, with the rotary embedding of q and k_new fused into the append launch
+// (fa_paged_rope.h), umfa_varlen_kvcache_attention_rope_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
 // the device, so a captured graph follows their contents on replay.  Launch order on the stream: the packed append of k_new / v_new
 // (when given), the item-list pre-pass, the attention, and with split-KV the fold.  The item list and the split partials come from the
 // stream's pooled workspace (a capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION: warm up first).  Anything
@@ -8,6 +9,7 @@
 
 #include "runtime_internal.h"
 #include "fa_paged_varlen.h"
+#include "fa_paged_rope.h"
 
 using namespace umfa;
 using namespace umfa_rt;
@@ -46,17 +48,20 @@ constexpr size_t PV_HDR_B = 256;  // the tally's words at the front of the works
 
 }  // namespace
 
-mfa_error_t umfa_varlen_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
-                                                         void* k_cache, const int64_t* k_cache_strides, void* v_cache,
-                                                         const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
-                                                         const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
-                                                         int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
-                                                         uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new,
-                                                         uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
-                                                         uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
-                                                         int32_t input_precision, void* out, int32_t out_precision, float* lse,
-                                                         int32_t num_splits) {
+namespace {
+
+// both entries; rope != NULL: the fused pre-pass (fa_paged_rope.h) stands in for the packed append and the attention reads its q image
+mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache,
+                                   const int64_t* k_cache_strides, void* v_cache, const int64_t* v_cache_strides, const void* k_new,
+                                   const int64_t* k_new_strides, const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                   int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q, uint32_t batch,
+                                   uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads,
+                                   uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                   uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision, void* out,
+                                   int32_t out_precision, float* lse, int32_t num_splits, const RopeArgs* rope) {
     Context* ctx = as_ctx(context);
+    if (rope && (!has_new || !rope->cos || !rope->sin || rope->table_f32 < 0))
+        return MFA_ERROR_INVALID_ARGS;
     if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !cu_seqlens_q || !k_cache_strides || !v_cache_strides)
         return MFA_ERROR_INVALID_ARGS;
     if (input_precision != MFA_PRECISION_FP16 && input_precision != MFA_PRECISION_BF16) return MFA_ERROR_INVALID_ARGS;
@@ -102,23 +107,76 @@ mfa_error_t umfa_varlen_kvcache_attention_forward_stream(mfa_context_t context, 
     DeviceGuard guard(dev);
     p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : pv_auto_splits(v, pv_cu_count(dev));
     if (!paged_varlen_supported(v)) return MFA_ERROR_INVALID_ARGS;
-    if (v.n_items) {
-        // one block of the pooled workspace: the form tally (PV_HDR_B bytes), the item list, then (split) the partials
+    PagedRopeParams r;
+    memset(&r, 0, sizeof(r));
+    if (rope) {
+        paged_rope_fill(r, *rope);
+        r.packed = 1;
+        r.v = v;
+    }
+    if (v.n_items || (rope && total_q)) {
+        // one block of the pooled workspace: the form tally (PV_HDR_B bytes), the item list, (split) the partials, then (rotary) the
+        // rotated q image; every check and the allocation come before the first launch
         StreamScratch& sc = ctx->pool(dev, (hipStream_t)stream);
         const size_t list_b = ((size_t)v.n_items * 2 * sizeof(int32_t) + 255) & ~(size_t)255;
-        const size_t part_b = p.nsplit > 1 ? (size_t)p.nsplit * total_q * num_heads * (p.D + 2) * sizeof(float) : 0;
-        char* const ws = (char*)sc.workspace.ensure(PV_HDR_B + list_b + part_b, (hipStream_t)stream);
+        const size_t part_b = p.nsplit > 1 ? (size_t)p.nsplit * total_q * num_heads * (p.D + 2) * sizeof(float) : 0;  // (a multiple of 8 bytes)
+        const size_t img_at = (PV_HDR_B + list_b + part_b + 255) & ~(size_t)255;
+        const size_t need = rope ? img_at + paged_rope_qimg_bytes(r) : PV_HDR_B + list_b + part_b;  // without rotary: the size it always was
+        char* const ws = (char*)sc.workspace.ensure(need, (hipStream_t)stream);
         if (!ws) return MFA_ERROR_MEMORY_ALLOCATION;
         v.counts = (uint32_t*)ws;
         v.items = (int32_t*)(ws + PV_HDR_B);
         if (part_b) p.part = (float*)(ws + PV_HDR_B + list_b);
+        r.qimg = ws + img_at;
     }
-    if (has_new) {
+    if (rope) {
+        if (total_q) {
+            if (!paged_rope_supported(r)) return MFA_ERROR_INVALID_ARGS;
+            if (const hipError_t e = launch_paged_rope(r, (hipStream_t)stream); e != hipSuccess) return rc_pv(e);
+            p.q = r.qimg;
+            p.qst = (int64_t)num_heads * head_dim; p.qsh = head_dim;
+        }
+    } else if (has_new) {
         if (const hipError_t e = launch_paged_varlen_append(v, (hipStream_t)stream); e != hipSuccess) return rc_pv(e);
     }
     const hipError_t e = launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
     ctx->last_kernel = name;
     return rc_pv(e);
+}
+
+}  // namespace
+
+mfa_error_t umfa_varlen_kvcache_attention_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                         void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                         const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                         const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                         int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+                                                         uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new,
+                                                         uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
+                                                         uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                         int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                         int32_t num_splits) {
+    return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
+                                  v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
+                                  cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
+                                  softmax_scale, causal, input_precision, out, out_precision, lse, num_splits, nullptr);
+}
+
+mfa_error_t umfa_varlen_kvcache_attention_rope_forward_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache, const int64_t* k_cache_strides,
+    void* v_cache, const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides, const void* v_new,
+    const int64_t* v_new_strides, const int32_t* block_table, int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+    uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads, uint32_t num_kv_heads,
+    uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+    int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const void* rotary_cos,
+    const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
+    bool rotary_interleaved) {
+    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
+    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
+                                  v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
+                                  cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
+                                  softmax_scale, causal, input_precision, out, out_precision, lse, num_splits, &rope);
 }
 
 // debug: the tally of the last umfa_varlen_kvcache_attention_forward_stream call on `stream` (nothing else may have used the stream's

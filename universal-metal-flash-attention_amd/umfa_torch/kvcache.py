@@ -14,6 +14,10 @@ v_descale, device fp32 tensors that broadcast to [B, H_kv] (a Python float becom
 e4m3fn(byte) * descale[b, h_kv], k / v are quantised on the way in, q and O stay 16-bit.  The `umfa::kvcache_fp8_forward` /
 `umfa::kvcache_fp8_forward_append` ops serve them.  The descales stay on the device like the lengths.
 
+Rotary embedding: with rotary_cos / rotary_sin the append launch also rotates k on its way into the cache and q
+into a workspace image, at positions read from cache_seqlens on the device; the `umfa::kvcache_rope_forward_append` /
+`umfa::kvcache_fp8_rope_forward_append` ops serve those calls, which launch as many kernels as the same call without rotary.
+
 Scope: fp16 / bf16 device tensors (fp8 caches as above), head_dim 64 / 128, forward only (a backward through these ops raises).  Anything
 else raises ValueError: there is no fall-back.
 """
@@ -106,8 +110,46 @@ def _(q, k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, block_tabl
     return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
 
 
+@torch.library.custom_op("umfa::kvcache_rope_forward_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def kvcache_rope_forward_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                                cache_seqlens: torch.Tensor, rotary_cos: torch.Tensor, rotary_sin: torch.Tensor, rotary_interleaved: bool,
+                                block_table: Optional[torch.Tensor], causal: bool, scale: float,
+                                num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kvcache_forward_append with the rotary embedding fused into the append launch (umfa_kvcache_attention_rope_forward_stream): k is
+    rotated at cache_seqlens[b] + t on its way into k_cache, q at cache_seqlens[b] + i (causal) or cache_seqlens[b] (not)."""
+    return ops.kvcache_attention_rope_forward(_kernel_view(q), k_cache, v_cache, cache_seqlens, rotary_cos, rotary_sin, block_table,
+                                              _kernel_view(k), _kernel_view(v), scale=float(scale), causal=bool(causal),
+                                              num_splits=int(num_splits), rotary_interleaved=bool(rotary_interleaved))
+
+
+@kvcache_rope_forward_append.register_fake
+def _(q, k_cache, v_cache, k, v, cache_seqlens, rotary_cos, rotary_sin, rotary_interleaved, block_table, causal, scale, num_splits):
+    B, Sq, H, D = q.shape
+    return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
+
+
+@torch.library.custom_op("umfa::kvcache_fp8_rope_forward_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def kvcache_fp8_rope_forward_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                                    cache_seqlens: torch.Tensor, k_descale: torch.Tensor, v_descale: torch.Tensor, rotary_cos: torch.Tensor,
+                                    rotary_sin: torch.Tensor, rotary_interleaved: bool, block_table: Optional[torch.Tensor], causal: bool,
+                                    scale: float, num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kvcache_fp8_forward_append (k_cache / v_cache the caches' uint8 views) with the rotary embedding fused into the quantising append
+    launch: the rotated k is rounded to q's dtype, then quantised."""
+    return ops.kvcache_attention_rope_forward(_kernel_view(q), k_cache.view(torch.float8_e4m3fn), v_cache.view(torch.float8_e4m3fn),
+                                              cache_seqlens, rotary_cos, rotary_sin, block_table, _kernel_view(k), _kernel_view(v),
+                                              scale=float(scale), causal=bool(causal), num_splits=int(num_splits),
+                                              rotary_interleaved=bool(rotary_interleaved), k_descale=k_descale, v_descale=v_descale)
+
+
+@kvcache_fp8_rope_forward_append.register_fake
+def _(q, k_cache, v_cache, k, v, cache_seqlens, k_descale, v_descale, rotary_cos, rotary_sin, rotary_interleaved, block_table, causal, scale,
+      num_splits):
+    B, Sq, H, D = q.shape
+    return q.new_empty((B, Sq, H, D)), q.new_empty((B, H, Sq), dtype=torch.float32)
+
+
 # flash_attn_with_kvcache arguments this entry accepts only at their defaults
-_UNSUPPORTED = {"rotary_cos": None, "rotary_sin": None, "cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
+_UNSUPPORTED = {"cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
                 "softcap": 0.0, "alibi_slopes": None}
 
 
@@ -152,6 +194,40 @@ def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table, fp8=False):
         bad(f"cache_seqlens must be contiguous (got stride {cache_seqlens.stride(0)}): pass cache_seqlens.contiguous()")
 
 
+def _check_rotary(fn, q, k, new_tokens, rotary_cos, rotary_sin):
+    """the rotary tables of kvcache_attention / varlen_kvcache_attention: True when the call is a rotary one"""
+    def bad(msg):
+        raise ValueError(f"{fn}: {msg}")
+
+    if rotary_cos is None and rotary_sin is None:
+        return False
+    if rotary_cos is None or rotary_sin is None:
+        bad("rotary_cos and rotary_sin must be given together")
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or not isinstance(q, torch.Tensor) or t.device != q.device or not t.is_cuda:
+            bad(f"{name} must be a 2-D [seqlen_ro, rotary_dim / 2] tensor on q's device (got {tuple(getattr(t, 'shape', ()))}, "
+                f"{getattr(t, 'device', None)})")
+    if rotary_cos.shape != rotary_sin.shape or rotary_cos.dtype != rotary_sin.dtype:
+        bad(f"rotary_cos and rotary_sin must match in shape and dtype (got {tuple(rotary_cos.shape)} {rotary_cos.dtype}, "
+            f"{tuple(rotary_sin.shape)} {rotary_sin.dtype})")
+    if rotary_cos.dtype not in (torch.float32, q.dtype):
+        bad(f"the rotary tables must be fp32 or q's dtype {q.dtype} (got {rotary_cos.dtype})")
+    if not new_tokens:
+        bad("rotary_cos / rotary_sin need new tokens k / v (flash-attention's rule): there is nothing to rotate into the cache")
+    seqlen_ro, rotary_dim = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    if rotary_dim < 16 or rotary_dim > q.shape[-1] or rotary_dim % 16:
+        bad(f"rotary_dim = 2 * rotary_cos.shape[1] must be a multiple of 16 in [16, head_dim = {q.shape[-1]}] (got {rotary_dim})")
+    if seqlen_ro == 0:
+        bad("the rotary tables hold no position (seqlen_ro = 0)")
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        aligned = torch.compiler.is_compiling() or t.data_ptr() % 16 == 0
+        if t.stride(1) != 1 or (t.stride(0) * t.element_size()) % 16 or t.stride(0) < t.shape[1] or not aligned:
+            bad(f"{name} needs a unit column stride and 16-byte aligned rows (got strides {t.stride()}): pass {name}.contiguous()")
+    if rotary_cos.stride() != rotary_sin.stride():
+        bad("rotary_cos and rotary_sin must have equal strides")
+    return True
+
+
 def _descale(d, q, Hkv, name):
     """a descale argument as the device fp32 tensor the op takes: None = 1.0, a Python number becomes a one-element tensor (a fill on
     the device, no synchronisation), a tensor must be device fp32 and broadcast to [B, H_kv]"""
@@ -171,20 +247,24 @@ def _descale(d, q, Hkv, name):
 def kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: Optional[torch.Tensor] = None,
                       v: Optional[torch.Tensor] = None, cache_seqlens=None, block_table: Optional[torch.Tensor] = None,
                       softmax_scale: Optional[float] = None, causal: bool = False, num_splits: int = 0,
-                      return_softmax_lse: bool = False, k_descale=None, v_descale=None, **unsupported):
+                      return_softmax_lse: bool = False, k_descale=None, v_descale=None, rotary_cos: Optional[torch.Tensor] = None,
+                      rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False, **unsupported):
     """flash_attn_with_kvcache on the MFMA kernels: softmax(q k^T scale [bottom-right causal]) v over each sequence's cached keys,
     after appending k / v into the cache in place.  Returns O [B, Sq, H, D] in q's dtype, or (O, LSE [B, H, Sq] fp32) with
     return_softmax_lse.  cache_seqlens: an int (broadcast to every sequence) or a device int32 [B]; None = the whole capacity.
     k_cache / v_cache both torch.float8_e4m3fn: k_descale / v_descale (a float, or a device fp32 tensor that broadcasts to [B, H_kv];
     default 1.0) give the value of a byte, e4m3fn(byte) * descale[b, h_kv], and k / v are quantised into the cache; with a 16-bit cache
     they must stay None.
-    rotary_cos / rotary_sin / cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes are accepted at their defaults only.
+    rotary_cos / rotary_sin: device tables [seqlen_ro, rotary_dim / 2], fp32 or q's dtype, rotary_dim a
+    multiple of 16 in [16, D]; with them k is rotated at positions cache_seqlens[b] + t on its way into the cache and q at
+    cache_seqlens[b] + i (causal) or cache_seqlens[b] (not causal), inside the append launch -- bit for bit the call on rotated q / k.
+    rotary_interleaved: pairs (2i, 2i + 1) instead of (i, i + rotary_dim / 2); ignored without tables.  k / v are required; a position
+    at or past seqlen_ro takes the last table row.
+    cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes are accepted at their defaults only.
     Raises ValueError outside the kernels' scope (see the module docstring)."""
     for name, val in unsupported.items():
-        if name not in _UNSUPPORTED and name != "rotary_interleaved":
+        if name not in _UNSUPPORTED:
             raise TypeError(f"kvcache_attention() got an unexpected keyword argument '{name}'")
-        if name == "rotary_interleaved":
-            continue  # (only meaningful with rotary_cos, which is refused below)
         default = _UNSUPPORTED[name]
         same = val is None if default is None else (tuple(val) == default if name == "window_size" else val == default)
         if not same:
@@ -202,18 +282,25 @@ def kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     if not fp8 and (k_descale is not None or v_descale is not None):
         raise ValueError("kvcache_attention: k_descale / v_descale go with float8_e4m3fn caches only")
     _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table, fp8)
+    rotary = _check_rotary("kvcache_attention", q, k, k is not None and k.shape[1] > 0, rotary_cos, rotary_sin)
     sm = float(softmax_scale) if softmax_scale is not None else float(q.shape[-1]) ** -0.5
     if fp8:
         kd, vd = (_descale(d, q, k_cache.shape[2], n) for d, n in ((k_descale, "k_descale"), (v_descale, "v_descale")))
         k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)  # (the ops take the bytes: kvcache_fp8_forward)
-        if k is not None and k.shape[1] > 0:
+        if rotary:
+            out, lse = torch.ops.umfa.kvcache_fp8_rope_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, kd, vd, rotary_cos, rotary_sin,
+                                                                      bool(rotary_interleaved), block_table, bool(causal), sm, int(num_splits))
+        elif k is not None and k.shape[1] > 0:
             out, lse = torch.ops.umfa.kvcache_fp8_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, kd, vd, block_table, bool(causal),
                                                                  sm, int(num_splits))
         else:
             out, lse = torch.ops.umfa.kvcache_fp8_forward(q, k_cache, v_cache, cache_seqlens, kd, vd, block_table, bool(causal), sm,
                                                           int(num_splits))
         return (out, lse) if return_softmax_lse else out
-    if k is not None and k.shape[1] > 0:
+    if rotary:
+        out, lse = torch.ops.umfa.kvcache_rope_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, rotary_cos, rotary_sin,
+                                                              bool(rotary_interleaved), block_table, bool(causal), sm, int(num_splits))
+    elif k is not None and k.shape[1] > 0:
         out, lse = torch.ops.umfa.kvcache_forward_append(q, k_cache, v_cache, k, v, cache_seqlens, block_table, bool(causal), sm,
                                                          int(num_splits))
     else:

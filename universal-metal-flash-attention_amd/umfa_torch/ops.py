@@ -573,8 +573,36 @@ def varlen_attention_backward(dout, q, k, v, out, lse, cu_seq_q, cu_seq_k, max_q
     return dq, dk, dv
 
 
-def _kvcache_forward(entry, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype):
-    """the call both KV-cache entries share; extra: the arguments behind num_splits (the fp8 entry's descales)"""
+def _rope_args(name, q, cos, sin, interleaved):
+    """the rotary tail of the *_rope_forward_stream entries: (cos, sin, table precision, row stride, seqlen_ro, rotary_dim, interleaved)"""
+    if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor) or cos.dim() != 2 or cos.shape != sin.shape \
+            or cos.dtype != sin.dtype or cos.device != q.device or sin.device != q.device or cos.dtype not in (torch.float32, q.dtype):
+        raise ValueError(f"{name}: rotary_cos / rotary_sin must be equal-shaped [seqlen_ro, rotary_dim / 2] tensors on q's device, fp32 or q's dtype")
+    if cos.shape[0] == 0 or cos.stride() != sin.stride() or (cos.shape[1] > 1 and cos.stride(1) != 1) \
+            or (cos.stride(0) * cos.element_size()) % 16 or cos.data_ptr() % 16 or sin.data_ptr() % 16:
+        raise ValueError(f"{name}: the rotary tables need seqlen_ro > 0, a unit column stride, equal strides and 16-byte aligned rows")
+    return (ctypes.c_void_p(cos.data_ptr()), ctypes.c_void_p(sin.data_ptr()), _PREC[cos.dtype], int(cos.stride(0)), int(cos.shape[0]),
+            2 * int(cos.shape[1]), bool(interleaved))
+
+
+def _out_buffers(name, q, o_shape, lse_shape, out_dtype, out, lse):
+    """(out, lse) of a KV-cache call: fresh tensors, or the caller's -- dense, 16-byte aligned, of the right shape, dtype and device"""
+    if out is None:
+        out = torch.empty(o_shape, dtype=out_dtype or q.dtype, device=q.device)
+    elif tuple(out.shape) != tuple(o_shape) or out.dtype not in (q.dtype, torch.float32) or out.device != q.device or not out.is_contiguous() \
+            or out.data_ptr() % 16:
+        raise ValueError(f"{name}: out must be a dense, 16-byte aligned {tuple(o_shape)} tensor in q's dtype or fp32 on q's device")
+    if lse is None:
+        lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
+    elif tuple(lse.shape) != tuple(lse_shape) or lse.dtype != torch.float32 or lse.device != q.device or not lse.is_contiguous():
+        raise ValueError(f"{name}: lse must be a dense fp32 {tuple(lse_shape)} tensor on q's device")
+    return out, lse
+
+
+def _kvcache_forward(entry, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype,
+                     out=None, lse=None):
+    """the call the KV-cache entries share; extra: the arguments behind num_splits (the fp8 entry's descales, the rotary entry's tail);
+    out / lse: the caller's buffers (_out_buffers)"""
     B, Sq, H, D = q.shape
     if B > 1 and (cache_seqlens.stride(0) != 1 or (block_table is not None and block_table.stride(1) != 1)):
         raise ValueError("kvcache_attention_forward: cache_seqlens and the rows of block_table must be contiguous")
@@ -584,8 +612,7 @@ def _kvcache_forward(entry, extra, q, k_cache, v_cache, cache_seqlens, block_tab
     else:
         max_pages, bt_stride, bt = 1, 0, None
     Snew = 0 if k_new is None else k_new.shape[1]
-    out = torch.empty((B, Sq, H, D), dtype=out_dtype or q.dtype, device=q.device)
-    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    out, lse = _out_buffers("kvcache_attention_forward", q, (B, Sq, H, D), (B, H, Sq), out_dtype, out, lse)
     stream = torch.cuda.current_stream(q.device).cuda_stream
     new = [None, None, None, None]
     if Snew:
@@ -638,6 +665,64 @@ def kvcache_attention_fp8_forward(q, k_cache, v_cache, cache_seqlens, k_descale,
                             v_new, scale, causal, num_splits, out_dtype)
 
 
+def kvcache_attention_rope_forward(q, k_cache, v_cache, cache_seqlens, rotary_cos, rotary_sin, block_table=None, k_new=None, v_new=None, *,
+                                   scale: float, causal: bool = False, num_splits: int = 0, rotary_interleaved: bool = False,
+                                   k_descale=None, v_descale=None, out_dtype=None, out=None, lse=None):
+    """kvcache_attention_forward (16-bit caches) or kvcache_attention_fp8_forward (float8_e4m3fn caches with k_descale / v_descale) with
+    the rotary embedding of q and k_new fused into the append launch (umfa_kvcache_attention_rope_forward_stream): k_new is rotated at
+    positions cache_seqlens[b] + t on its way into the cache, q at cache_seqlens[b] + i (causal) or cache_seqlens[b] (not) into a
+    workspace image the attention reads; v_new is appended as it is.  rotary_cos / rotary_sin device [seqlen_ro, rotary_dim / 2], fp32
+    or q's dtype, unit column stride, 16-byte aligned rows; rotary_dim a multiple of 16 in [16, D].  New tokens are required.  Bit for
+    bit the plain call on rotated, rounded q and k_new.  Positions are never read back.  out / lse: optional dense buffers
+    [B, Sq, H, D] / fp32 [B, H, Sq] to write into."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if fp8 != (v_cache.dtype == torch.float8_e4m3fn) or q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError("kvcache_attention_rope_forward: q must be fp16 / bf16 and the caches both 16-bit or both float8_e4m3fn")
+    if k_new is None or v_new is None or k_new.shape[1] == 0:
+        raise ValueError("kvcache_attention_rope_forward: rotary needs new tokens (k_new / v_new)")
+    if fp8:
+        B, Hkv = q.shape[0], k_cache.shape[2]
+        desc = (*_descale_arg(k_descale, B, Hkv, "k_descale"), *_descale_arg(v_descale, B, Hkv, "v_descale"))
+    elif k_descale is not None or v_descale is not None:
+        raise ValueError("kvcache_attention_rope_forward: k_descale / v_descale go with float8_e4m3fn caches only")
+    else:
+        desc = (None, None, None, None)
+    extra = (bool(fp8), *desc, *_rope_args("kvcache_attention_rope_forward", q, rotary_cos, rotary_sin, rotary_interleaved))
+    return _kvcache_forward(_lib.umfa_kvcache_attention_rope_forward_stream, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new,
+                            v_new, scale, causal, num_splits, out_dtype, out, lse)
+
+
+def _varlen_kvcache_forward(name, entry, extra, q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale,
+                            causal, num_splits, out_dtype, out=None, lse=None):
+    """the call both packed KV-cache entries share; name: the public wrapper (for messages); extra: the arguments behind num_splits (the
+    rotary entry's tail); out / lse: the caller's buffers (_out_buffers)"""
+    Tq, H, D = q.shape
+    B = cu_seqlens_q.numel() - 1
+    if cu_seqlens_q.dim() != 1 or B < 1 or cache_seqlens.shape != (B,) or cu_seqlens_q.stride(0) != 1 or (B > 1 and cache_seqlens.stride(0) != 1) \
+            or (block_table is not None and (block_table.shape[0] != B or block_table.stride(1) != 1)):
+        raise ValueError(f"{name}: cu_seqlens_q [B + 1], cache_seqlens [B] and the rows of block_table [B, .] must be contiguous")
+    num_pages, page_size, Hkv = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    if block_table is not None:
+        max_pages, bt_stride, bt = block_table.shape[1], block_table.stride(0), ctypes.c_void_p(block_table.data_ptr())
+    else:
+        max_pages, bt_stride, bt = 1, 0, None
+    has_new = k_new is not None
+    out, lse = _out_buffers(name, q, (Tq, H, D), (H, Tq), out_dtype, out, lse)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    new = [None, None, None, None]
+    if has_new:
+        if k_new.shape != (Tq, Hkv, D) or v_new.shape != (Tq, Hkv, D):
+            raise ValueError(f"{name}: k_new / v_new must be [T_q, H_kv, D] = {(Tq, Hkv, D)}")
+        new = [ctypes.c_void_p(k_new.data_ptr()), _i64(k_new.stride()[:2]), ctypes.c_void_p(v_new.data_ptr()), _i64(v_new.stride()[:2])]
+    _check_error(entry(
+        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]), ctypes.c_void_p(k_cache.data_ptr()),
+        _i64(k_cache.stride()[:3]), ctypes.c_void_p(v_cache.data_ptr()), _i64(v_cache.stride()[:3]), *new, bt, int(bt_stride),
+        ctypes.c_void_p(cache_seqlens.data_ptr()), Tq, B, int(max_seqlen_q), ctypes.c_void_p(cu_seqlens_q.data_ptr()), bool(has_new), H, Hkv, D,
+        int(page_size), int(num_pages), int(max_pages), float(scale), bool(causal), _PREC[q.dtype], ctypes.c_void_p(out.data_ptr()),
+        _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()), int(num_splits), *extra))
+    return out, lse
+
+
 def varlen_kvcache_attention_forward(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, block_table=None, k_new=None,
                                      v_new=None, *, scale: float, causal: bool = False, num_splits: int = 0, out_dtype=None):
     """O [T_q, H, D] and LSE [H, T_q] (fp32, natural log) of packed variable-length queries over a paged or static KV cache
@@ -645,33 +730,24 @@ def varlen_kvcache_attention_forward(q, k_cache, v_cache, cu_seqlens_q, max_seql
     cache in place first.  q [T_q, H, D] with a contiguous head_dim and token / head strides that are multiples of 8 elements;
     cu_seqlens_q device int32 [B + 1]; max_seqlen_q a host int; the caches, block_table and cache_seqlens as kvcache_attention_forward
     takes them.  Asynchronous on torch's current stream; cu_seqlens_q, cache_seqlens and block_table are never read back."""
-    Tq, H, D = q.shape
-    B = cu_seqlens_q.numel() - 1
-    if cu_seqlens_q.dim() != 1 or B < 1 or cache_seqlens.shape != (B,) or cu_seqlens_q.stride(0) != 1 or (B > 1 and cache_seqlens.stride(0) != 1) \
-            or (block_table is not None and (block_table.shape[0] != B or block_table.stride(1) != 1)):
-        raise ValueError("varlen_kvcache_attention_forward: cu_seqlens_q [B + 1], cache_seqlens [B] and the rows of block_table [B, .] "
-                         "must be contiguous")
-    num_pages, page_size, Hkv = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
-    if block_table is not None:
-        max_pages, bt_stride, bt = block_table.shape[1], block_table.stride(0), ctypes.c_void_p(block_table.data_ptr())
-    else:
-        max_pages, bt_stride, bt = 1, 0, None
-    has_new = k_new is not None
-    out = torch.empty((Tq, H, D), dtype=out_dtype or q.dtype, device=q.device)
-    lse = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    new = [None, None, None, None]
-    if has_new:
-        if k_new.shape != (Tq, Hkv, D) or v_new.shape != (Tq, Hkv, D):
-            raise ValueError(f"varlen_kvcache_attention_forward: k_new / v_new must be [T_q, H_kv, D] = {(Tq, Hkv, D)}")
-        new = [ctypes.c_void_p(k_new.data_ptr()), _i64(k_new.stride()[:2]), ctypes.c_void_p(v_new.data_ptr()), _i64(v_new.stride()[:2])]
-    _check_error(_lib.umfa_varlen_kvcache_attention_forward_stream(
-        context(), ctypes.c_void_p(stream), ctypes.c_void_p(q.data_ptr()), _i64(q.stride()[:2]), ctypes.c_void_p(k_cache.data_ptr()),
-        _i64(k_cache.stride()[:3]), ctypes.c_void_p(v_cache.data_ptr()), _i64(v_cache.stride()[:3]), *new, bt, int(bt_stride),
-        ctypes.c_void_p(cache_seqlens.data_ptr()), Tq, B, int(max_seqlen_q), ctypes.c_void_p(cu_seqlens_q.data_ptr()), bool(has_new), H, Hkv, D,
-        int(page_size), int(num_pages), int(max_pages), float(scale), bool(causal), _PREC[q.dtype], ctypes.c_void_p(out.data_ptr()),
-        _PREC[out.dtype], ctypes.c_void_p(lse.data_ptr()), int(num_splits)))
-    return out, lse
+    return _varlen_kvcache_forward("varlen_kvcache_attention_forward", _lib.umfa_varlen_kvcache_attention_forward_stream, (), q, k_cache,
+                                   v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits,
+                                   out_dtype)
+
+
+def varlen_kvcache_attention_rope_forward(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, rotary_cos, rotary_sin,
+                                          block_table=None, k_new=None, v_new=None, *, scale: float, causal: bool = False,
+                                          num_splits: int = 0, rotary_interleaved: bool = False, out_dtype=None, out=None, lse=None):
+    """varlen_kvcache_attention_forward with the rotary embedding of q and k_new fused into the packed append launch
+    (umfa_varlen_kvcache_attention_rope_forward_stream): packed row t of sequence b is rotated at cache_seqlens[b] + (t - cu[b]) (the
+    queries of a non-causal call all at cache_seqlens[b]).  Tables and rules as kvcache_attention_rope_forward; 16-bit caches.  out / lse:
+    optional dense buffers [T_q, H, D] / fp32 [H, T_q] to write into (rows no sequence covers stay as they were)."""
+    name = "varlen_kvcache_attention_rope_forward"
+    if k_new is None or v_new is None:
+        raise ValueError(f"{name}: rotary needs new tokens (k_new / v_new)")
+    rope = _rope_args(name, q, rotary_cos, rotary_sin, rotary_interleaved)
+    return _varlen_kvcache_forward(name, _lib.umfa_varlen_kvcache_attention_rope_forward_stream, rope, q, k_cache, v_cache, cu_seqlens_q,
+                                   max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype, out, lse)
 
 
 def varlen_kvcache_item_counts(device=None):

@@ -12,6 +12,10 @@ items) and decode / speculative sequences (the decode form) together; work follo
 the table stay on the device: no call synchronises, and a captured graph follows their contents on replay.  Lengths, cu values and table
 entries outside their ranges are clamped / masked on the device.
 
+Rotary embedding: with rotary_cos / rotary_sin the packed append launch also rotates k on its way into the cache
+and q into a workspace image, at positions read from cache_seqlens and cu_seqlens_q on the device
+(`umfa::varlen_kvcache_rope_forward_append`); such a call launches as many kernels as the same call without rotary.
+
 Scope: fp16 / bf16 device tensors, head_dim 64 / 128, forward only (a backward through these ops raises).  Anything else raises
 ValueError: there is no fall-back.
 """
@@ -22,7 +26,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import ops
-from .kvcache import KVCACHE_HEAD_DIMS, _DTYPES, _strides_ok
+from .kvcache import KVCACHE_HEAD_DIMS, _DTYPES, _check_rotary, _strides_ok
 
 
 def _packed_view(t: torch.Tensor) -> torch.Tensor:
@@ -62,8 +66,28 @@ def _(q, k_cache, v_cache, k, v, cu_seqlens_q, max_seqlen_q, cache_seqlens, bloc
     return q.new_empty((Tq, H, D)), q.new_empty((H, Tq), dtype=torch.float32)
 
 
+@torch.library.custom_op("umfa::varlen_kvcache_rope_forward_append", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def varlen_kvcache_rope_forward_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                                       cu_seqlens_q: torch.Tensor, max_seqlen_q: int, cache_seqlens: torch.Tensor, rotary_cos: torch.Tensor,
+                                       rotary_sin: torch.Tensor, rotary_interleaved: bool, block_table: Optional[torch.Tensor], causal: bool,
+                                       scale: float, num_splits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """varlen_kvcache_forward_append with the rotary embedding fused into the packed append launch
+    (umfa_varlen_kvcache_attention_rope_forward_stream): row t of sequence b is rotated at cache_seqlens[b] + (t - cu[b])."""
+    return ops.varlen_kvcache_attention_rope_forward(_packed_view(q), k_cache, v_cache, cu_seqlens_q, int(max_seqlen_q), cache_seqlens,
+                                                     rotary_cos, rotary_sin, block_table, _packed_view(k), _packed_view(v), scale=float(scale),
+                                                     causal=bool(causal), num_splits=int(num_splits),
+                                                     rotary_interleaved=bool(rotary_interleaved))
+
+
+@varlen_kvcache_rope_forward_append.register_fake
+def _(q, k_cache, v_cache, k, v, cu_seqlens_q, max_seqlen_q, cache_seqlens, rotary_cos, rotary_sin, rotary_interleaved, block_table, causal,
+      scale, num_splits):
+    Tq, H, D = q.shape
+    return q.new_empty((Tq, H, D)), q.new_empty((H, Tq), dtype=torch.float32)
+
+
 # flash_attn_varlen_func / flash_attn_with_kvcache arguments this entry accepts only at their defaults
-_UNSUPPORTED = {"rotary_cos": None, "rotary_sin": None, "cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
+_UNSUPPORTED = {"cache_batch_idx": None, "cache_leftpad": None, "window_size": (-1, -1),
                 "softcap": 0.0, "alibi_slopes": None, "seqused_k": None, "dropout_p": 0.0}
 
 
@@ -123,17 +147,21 @@ def _check(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block
 def varlen_kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, cu_seqlens_q: torch.Tensor, max_seqlen_q: int,
                              cache_seqlens: torch.Tensor, block_table: Optional[torch.Tensor] = None, k: Optional[torch.Tensor] = None,
                              v: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, causal: bool = False,
-                             num_splits: int = 0, return_softmax_lse: bool = False, **unsupported):
+                             num_splits: int = 0, return_softmax_lse: bool = False, rotary_cos: Optional[torch.Tensor] = None,
+                             rotary_sin: Optional[torch.Tensor] = None, rotary_interleaved: bool = False, **unsupported):
     """softmax(q k^T scale [bottom-right causal]) v for packed queries q [T_q, H, D] (sequence b = rows cu_seqlens_q[b] ..
     cu_seqlens_q[b+1] - 1) over each sequence's cached keys, after appending the packed k / v [T_q, H_kv, D] into the cache in place.
     Returns O [T_q, H, D] in q's dtype, or (O, LSE [H, T_q] fp32) with return_softmax_lse.  Rows no sequence covers are left unwritten.
-    rotary_cos / rotary_sin / cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes / seqused_k / dropout_p are accepted
-    at their defaults only.  Raises ValueError outside the kernels' scope (see the module docstring)."""
+    rotary_cos / rotary_sin: device tables [seqlen_ro, rotary_dim / 2], fp32 or q's dtype, rotary_dim a
+    multiple of 16 in [16, D]; with them row t of sequence b is rotated at cache_seqlens[b] + (t - cu_seqlens_q[b]) -- k on its way into
+    the cache, q into a workspace image (every query row of a non-causal call at cache_seqlens[b]) -- inside the append launch, bit for
+    bit the call on rotated q / k.  rotary_interleaved: pairs (2i, 2i + 1) instead of (i, i + rotary_dim / 2); ignored without tables.
+    k / v are required; a position at or past seqlen_ro takes the last table row.
+    cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes / seqused_k / dropout_p are accepted at their defaults only.
+    Raises ValueError outside the kernels' scope (see the module docstring)."""
     for name, val in unsupported.items():
-        if name not in _UNSUPPORTED and name != "rotary_interleaved":
+        if name not in _UNSUPPORTED:
             raise TypeError(f"varlen_kvcache_attention() got an unexpected keyword argument '{name}'")
-        if name == "rotary_interleaved":
-            continue  # (only meaningful with rotary_cos, which is refused below)
         default = _UNSUPPORTED[name]
         same = val is None if default is None else (tuple(val) == default if name == "window_size" else val == default)
         if not same:
@@ -142,7 +170,11 @@ def varlen_kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: to
     sm = float(softmax_scale) if softmax_scale is not None else float(q.shape[-1]) ** -0.5
     if not sm > 0.0:
         raise ValueError(f"varlen_kvcache_attention: softmax_scale must be positive (got {softmax_scale})")
-    if k is not None:
+    if _check_rotary("varlen_kvcache_attention", q, k, k is not None, rotary_cos, rotary_sin):
+        out, lse = torch.ops.umfa.varlen_kvcache_rope_forward_append(q, k_cache, v_cache, k, v, cu_seqlens_q, int(max_seqlen_q), cache_seqlens,
+                                                                     rotary_cos, rotary_sin, bool(rotary_interleaved), block_table,
+                                                                     bool(causal), sm, int(num_splits))
+    elif k is not None:
         out, lse = torch.ops.umfa.varlen_kvcache_forward_append(q, k_cache, v_cache, k, v, cu_seqlens_q, int(max_seqlen_q), cache_seqlens,
                                                                 block_table, bool(causal), sm, int(num_splits))
     else:
