@@ -66,20 +66,32 @@ def _f64(a):
     return a.astype(np.float64)
 
 
-def _softmax(Q, K, scale, causal):
+def _exp(Q, K, scale, causal):
+    """(exp(S - row max), its row sums [.., 1], the row max [.., 1])"""
     s = np.einsum("bhid,bhjd->bhij", Q, K) * scale
     if causal:
         Sq, Skv = s.shape[-2:]
         s = np.where(np.arange(Skv)[None, :] <= np.arange(Sq)[:, None], s, -np.inf)
     m = s.max(-1, keepdims=True)
     e = np.exp(s - m)
-    l = e.sum(-1, keepdims=True)
+    return e, e.sum(-1, keepdims=True), m
+
+
+def _softmax(Q, K, scale, causal):
+    e, l, m = _exp(Q, K, scale, causal)
     return e / l, (m + np.log(l))[..., 0]
 
 
-def forward(q, k, v, keep, p, *, scale, causal=False):
-    """fp64 O = s (keep o P) V and the undropped LSE [B, H, Sq]."""
+def forward(q, k, v, keep, p, *, scale, causal=False, kind=None):
+    """fp64 O = s (keep o P) V and the undropped LSE [B, H, Sq].
+
+    kind ('bf16' / 'fp16'): the FORMAT FLOOR instead of the exact O: keep o exp(S - the row's exact max) rounded once to `kind` in the
+    numerator only; the scores, the (undropped) denominator, s and V stay fp64.  V is taken as exact: a bf16 V enters the kernels' fp16
+    product as V 2^-e, exact except for values that fall into fp16's subnormals.  kind None: the exact values, unchanged."""
     Q, K, V = _f64(q), _f64(k), _f64(v)
+    if kind is not None:
+        e, l, m = _exp(Q, K, scale, causal)
+        return keep_scale(p) * np.einsum("bhij,bhjd->bhid", _round(e * keep, kind), V) / l, (m + np.log(l))[..., 0]
     P, lse = _softmax(Q, K, scale, causal)
     return keep_scale(p) * np.einsum("bhij,bhjd->bhid", P * keep, V), lse
 

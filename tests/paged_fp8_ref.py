@@ -57,9 +57,13 @@ def append(k8, v8, k_new, v_new, cache_seqlens, k_descale, v_descale, block_tabl
     return paged_ref.append(np.asarray(k8, np.uint8), np.asarray(v8, np.uint8), kq, vq, cache_seqlens, block_table)
 
 
-def forward(q, k8, v8, cache_seqlens, k_descale, v_descale, block_table=None, k_new=None, v_new=None, causal=False, scale=None):
+def forward(q, k8, v8, cache_seqlens, k_descale, v_descale, block_table=None, k_new=None, v_new=None, causal=False, scale=None, kind=None):
     """(O [B, Sq, H, D], LSE [B, H, Sq], k8', v8'): paged_ref.forward, one sequence at a time, on the cache dequantised with that
-    sequence's descales (a page shared by two sequences decodes under each one's own) and the quantised-then-dequantised new tokens"""
+    sequence's descales (a page shared by two sequences decodes under each one's own) and the quantised-then-dequantised new tokens.
+
+    kind ("fp16" / "bf16"): paged_ref.forward's format floor on the same dequantised post-append bytes (the append quantises, so the new
+    tokens enter as what was stored).  K8 and V8 are exact in both operand types, so only P rounds; V is taken as exact.  kind None: the
+    exact values, unchanged."""
     q = np.asarray(q, np.float64)
     k8, v8 = np.asarray(k8, np.uint8), np.asarray(v8, np.uint8)
     B, Sq, H, D = q.shape
@@ -77,7 +81,7 @@ def forward(q, k8, v8, cache_seqlens, k_descale, v_descale, block_table=None, k_
             kc, vc, bt = dequantise(k8[b:b + 1], dk), dequantise(v8[b:b + 1], dv), None
         else:
             kc, vc, bt = dequantise(k8, dk), dequantise(v8, dv), np.asarray(block_table)[b:b + 1]
-        o, l, _, _ = paged_ref.forward(q[b:b + 1], kc, vc, sl[b:b + 1], bt, kn, vn, causal, scale)
+        o, l, _, _ = paged_ref.forward(q[b:b + 1], kc, vc, sl[b:b + 1], bt, kn, vn, causal, scale, kind)
         out[b], lse[b] = o[0], l[0]
     k8n, v8n = append(k8, v8, k_new, v_new, cache_seqlens, k_descale, v_descale, block_table)
     return out, lse, k8n, v8n

@@ -77,8 +77,21 @@ def gather(k_cache, v_cache, cache_seqlens, S_new, block_table=None):
     return res
 
 
-def forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_new=None, causal=False, scale=None):
-    """(O [B, Sq, H, D], LSE [B, H, Sq], k_cache', v_cache') in fp64, the caches after the append"""
+def round_p(p, kind):
+    """the unnormalised P of the format floor: unchanged for kind None, else rounded once to `kind` ("fp16" / "bf16"), as fp64"""
+    if kind is None:
+        return p
+    from dropout_ref import _round  # (the one numpy restatement of the two 16-bit roundings the test references share)
+    return _round(np.asarray(p, np.float64), kind)
+
+
+def forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_new=None, causal=False, scale=None, kind=None):
+    """(O [B, Sq, H, D], LSE [B, H, Sq], k_cache', v_cache') in fp64, the caches after the append.
+
+    kind ("fp16" / "bf16"): the FORMAT FLOOR instead of the exact O -- what an ideal flash kernel gives (oracle.flash_format_floor's idea
+    on this module's visibility): P = exp(S - the row's exact max), rounded once to `kind`, in the numerator only; the scores, the
+    denominator and V stay fp64.  V is taken as exact: a bf16 V enters the kernels' fp16 product as V 2^-e, exact except for values that
+    fall into fp16's subnormals.  kind None returns the exact values, bit for bit what this function returned before it had the argument."""
     q = np.asarray(q, np.float64)
     B, Sq, H, D = q.shape
     scale = D ** -0.5 if scale is None else scale
@@ -102,7 +115,7 @@ def forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_
             p = np.where(vis, np.exp(s - m), 0.0)
             l = p.sum(1)
             with np.errstate(invalid="ignore", divide="ignore"):
-                o = (p @ V[:, h // G]) / l[:, None] if Lk else np.zeros((Sq, D))
+                o = (round_p(p, kind) @ V[:, h // G]) / l[:, None] if Lk else np.zeros((Sq, D))
                 lse[b, h] = np.where(live, np.log(l) + m[:, 0], -np.inf)
             out[b, :, h] = np.where(live[:, None], o, 0.0)
     return out, lse, kc, vc

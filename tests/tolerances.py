@@ -14,6 +14,8 @@ Two assertions, both independent of what any kernel measured last week:
      stale reference (fa_fwd16_w64 lazy / deferred max: a row's largest P is no      max <= 2.5 x floor,  rms <= 1.15 x floor
        longer exactly 1.0, so the dominant key takes the ordinary half-ulp too)
    The rms bound is the sharp one: a kernel that got 15 % worse everywhere fails it in every regime.
+   Forms the dense floor cannot express (paged, fp8, packed, banded, dropout) hand over the floor itself: their reference's
+   forward(kind=...) on the same elements (check_forward(floor=, regime=); tests/test_gpu_forward_floor.py, profiles/fwd_floor).
 2. FORMAT CEILING (every call, also without inputs: masks, windows, fuzz shapes): max <= one ulp of P at 1.0
    (2^-8 bf16, 2^-11 fp16), rms <= 0.6 of it.  The reference's own tolerances are 1e-2 (bf16) / 1e-3 (fp16)
    (examples/pytorch-custom-op-ffi/tests/conftest.py:186-199).
@@ -89,18 +91,27 @@ OUT_HALF_ULP = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11}
 
 
 def check_forward(o, ref, dt, kernel: str, tag: str = "", scale_max: float = 1.0, min_elems_for_rms: int = 4096,
-                  out_dt=None, inputs=None, rows=None, causal: bool = False, scale=None):
+                  out_dt=None, inputs=None, rows=None, causal: bool = False, scale=None, floor=None, regime=None):
     """Assert the forward parity bounds for one output against the oracle.
 
     o, ref: [B, H, R, D] (R = all query rows, or the subset `rows` of them).  kernel: umfa_torch.last_kernel() /
     ctx.last_kernel.  inputs = (q, k, v) as the oracle takes them (bf16 as uint16 bits): enables the floor-relative
     assertion on (a spread of <= 64 of) the same rows; rows / causal / scale describe them.  scale_max loosens the max
     bounds for deliberately hostile inputs (stated at the call site); out_dt: the element type O was stored in when it is
-    not fp32."""
+    not fp32.
+
+    floor: the ideal kernel's O on the SAME elements as o and ref (a reference's forward(kind=...): paged, packed, banded, dropout
+    forms that oracle.flash_format_floor cannot express); it takes the place of the flash_format_floor call (fp32 O only), every
+    element is compared, and an absolute allowance of BWD_EPS x max|O_ref| stands beside the multiples, as in check_backward, so that
+    elements whose floor error is exactly zero have a bound.  regime: overrides regime_of(kernel); a pair (regime of the max
+    multiple, regime of the rms multiple) holds forms that round P against several references (per-quarter, per-part) to the
+    "stale" max multiple -- sample noise of the max, taken as it stands without the small-sample widening -- and the "exact" rms one."""
     name = _name(dt)
     if name == "bf16" and "pv16" in kernel:
         name = "fp16"  # the format of P (and of V inside the kernel) decides the bounds
-    regime = regime_of(kernel)
+    regime = regime_of(kernel) if regime is None else regime
+    rmax, rrms = (regime, regime) if isinstance(regime, str) else regime
+    regime = rmax if rmax == rrms else f"{rmax}/{rrms}"
     mx, rms = errors(o, ref)
     # rms: 0.6 ulp -- a row that spreads over very many keys (S = 131072, flat) sits at the rounding level of P itself, ulp x 0.41 ...
     # 0.5 (measured with fp16 P: 0.503 ulp); the sharp rms bound is the floor-relative one below
@@ -113,7 +124,20 @@ def check_forward(o, ref, dt, kernel: str, tag: str = "", scale_max: float = 1.0
     rec = dict(dtype=name, kernel=kernel, regime=regime, out=_name(out_dt) if out_dt is not None else "fp32", max=mx, rms=rms,
                ceiling_max=cmax * scale_max, ceiling_rms=crms * scale_max, n=int(np.asarray(ref).size))
     fl = None
-    if inputs is not None and out_dt is None:
+    n_floor = np.asarray(ref)[:, :, :MAX_FLOOR_ROWS].size
+    eps_max = eps_rms = 0.0
+    if floor is not None:
+        assert out_dt is None, "the floor describes an fp32 O"
+        assert np.asarray(floor).shape == np.asarray(ref).shape, (np.asarray(floor).shape, np.asarray(ref).shape)
+        fmax, frms = errors(floor, ref)
+        fl = (fmax, frms, mx, rms)
+        n_floor = int(np.asarray(ref).size)
+        r64 = np.asarray(ref, np.float64)
+        eps_max = BWD_EPS  # (errors() is relative to max|O_ref| / rms(O_ref): the absolute allowance in those units)
+        eps_rms = BWD_EPS * float(np.abs(r64).max() / max(np.sqrt((r64 * r64).mean()), 1e-30))
+        rec.update(floor_max=fmax, floor_rms=frms, max_on_floor_rows=mx, rms_on_floor_rows=rms,
+                   ratio_max=mx / max(fmax, 1e-30), ratio_rms=rms / max(frms, 1e-30))
+    elif inputs is not None and out_dt is None:
         from oracle import oracle
         qb, kb, vb = inputs
         R = np.asarray(ref).shape[2]
@@ -132,12 +156,12 @@ def check_forward(o, ref, dt, kernel: str, tag: str = "", scale_max: float = 1.0
         assert rms < crms * scale_max, (tag, kernel, "format ceiling, rms", rms, crms * scale_max)
     if fl is not None:
         fmax, frms, kmax, krms = fl
-        mmax, mrms = FLOOR_MULT[regime]
-        if np.asarray(ref)[:, :, :MAX_FLOOR_ROWS].size < SMALL_SAMPLE:
+        mmax, mrms = FLOOR_MULT[rmax][0], FLOOR_MULT[rrms][1]
+        if n_floor < SMALL_SAMPLE and not (floor is not None and rmax == "stale"):
             mmax *= SMALL_SAMPLE_SLACK
-        assert kmax <= mmax * scale_max * fmax, (tag, kernel, regime, "max vs format floor", kmax, fmax, mmax * scale_max)
-        if np.asarray(ref)[:, :, :MAX_FLOOR_ROWS].size >= min_elems_for_rms:
-            assert krms <= mrms * scale_max * frms, (tag, kernel, regime, "rms vs format floor", krms, frms, mrms * scale_max)
+        assert kmax <= mmax * scale_max * fmax + eps_max, (tag, kernel, regime, "max vs format floor", kmax, fmax, mmax * scale_max)
+        if n_floor >= min_elems_for_rms:
+            assert krms <= mrms * scale_max * frms + eps_rms, (tag, kernel, regime, "rms vs format floor", krms, frms, mrms * scale_max)
     return mx, rms
 
 

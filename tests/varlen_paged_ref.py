@@ -64,8 +64,12 @@ def covered(cu, Tq, max_q):
     return cov
 
 
-def forward(q, k_cache, v_cache, cu, max_q, cache_seqlens, block_table=None, k_new=None, v_new=None, causal=False, scale=None):
-    """(O [T_q, H, D], LSE [H, T_q], k_cache', v_cache') in fp64, the caches after the append; rows no sequence covers stay 0 / -inf"""
+def forward(q, k_cache, v_cache, cu, max_q, cache_seqlens, block_table=None, k_new=None, v_new=None, causal=False, scale=None, kind=None):
+    """(O [T_q, H, D], LSE [H, T_q], k_cache', v_cache') in fp64, the caches after the append; rows no sequence covers stay 0 / -inf.
+
+    kind ("fp16" / "bf16"): the format floor (paged_ref.forward): P relative to the row's exact max, rounded once to `kind`, in the
+    numerator only; scores, denominator and V in fp64.  V is taken as exact: a bf16 V enters the kernels' fp16 product as V 2^-e, exact
+    except for values that fall into fp16's subnormals.  kind None: the exact values, unchanged."""
     q = np.asarray(q, np.float64)
     Tq, H, D = q.shape
     scale = D ** -0.5 if scale is None else scale
@@ -96,7 +100,7 @@ def forward(q, k_cache, v_cache, cu, max_q, cache_seqlens, block_table=None, k_n
             p = np.where(vis, np.exp(s - m), 0.0)
             l = p.sum(1)
             with np.errstate(invalid="ignore", divide="ignore"):
-                o = (p @ V[:, h // G]) / l[:, None] if Lk else np.zeros((Lq, D))
+                o = (paged_ref.round_p(p, kind) @ V[:, h // G]) / l[:, None] if Lk else np.zeros((Lq, D))
                 lse[h, q0:q0 + Lq] = np.where(live, np.log(l) + m[:, 0], -np.inf)
             out[q0:q0 + Lq, h] = np.where(live[:, None], o, 0.0)
     return out, lse, kc, vc

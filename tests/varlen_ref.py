@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from paged_ref import round_p
+
 
 def visible(Lq: int, Lk: int, causal: bool) -> np.ndarray:
     """bool [Lq, Lk]: which keys each query of one sequence sees"""
@@ -23,8 +25,10 @@ def seqs(cu_q, cu_k):
     return [(int(cu_q[n]), int(cu_q[n + 1] - cu_q[n]), int(cu_k[n]), int(cu_k[n + 1] - cu_k[n])) for n in range(len(cu_q) - 1)]
 
 
-def forward(q, k, v, cu_q, cu_k, causal: bool = False, scale=None):
-    """(O [T_q, H, D], LSE [H, T_q]) in fp64; rows no sequence covers stay 0 / -inf"""
+def forward(q, k, v, cu_q, cu_k, causal: bool = False, scale=None, kind=None):
+    """(O [T_q, H, D], LSE [H, T_q]) in fp64; rows no sequence covers stay 0 / -inf.  kind ("fp16" / "bf16"): the format floor instead --
+    P relative to the row's exact max, rounded once to `kind`, in the numerator only (scores, denominator and V in fp64; V is taken as
+    exact); kind None: the exact values, unchanged."""
     q, k, v = (np.asarray(a, np.float64) for a in (q, k, v))
     Tq, H, D = q.shape
     G = H // k.shape[1]
@@ -43,7 +47,7 @@ def forward(q, k, v, cu_q, cu_k, causal: bool = False, scale=None):
             p = np.exp(s - m)
             l = p.sum(1)
             with np.errstate(invalid="ignore", divide="ignore"):
-                o = (p @ v[k0:k0 + Lk, h // G]) / l[:, None]
+                o = (round_p(p, kind) @ v[k0:k0 + Lk, h // G]) / l[:, None]
                 lse[h, q0:q0 + Lq] = np.where(live, np.log(l) + m[:, 0], -np.inf)
             out[q0:q0 + Lq, h] = np.where(live[:, None], o, 0.0)
     return out, lse

@@ -39,9 +39,13 @@ def _with_window(fn, causal, window):
         varlen_ref.visible = saved
 
 
-def forward(q, k, v, cu_q, cu_k, causal: bool = False, window=(-1, -1), scale=None):
-    """(O [T_q, H, D], LSE [H, T_q]) in fp64; rows that see no key: O = 0, LSE = -inf"""
-    return _with_window(lambda: varlen_ref.forward(q, k, v, cu_q, cu_k, True, scale), causal, window)
+def forward(q, k, v, cu_q, cu_k, causal: bool = False, window=(-1, -1), scale=None, kind=None):
+    """(O [T_q, H, D], LSE [H, T_q]) in fp64; rows that see no key: O = 0, LSE = -inf.
+
+    kind ("fp16" / "bf16"): the FORMAT FLOOR on the band's visibility instead of the exact O: P = exp(S - the row's exact max over the keys
+    it sees), rounded once to `kind`, in the numerator only; scores, denominator and V stay fp64.  V is taken as exact: a bf16 V enters the
+    kernels' fp16 product as V 2^-e, exact except for values that fall into fp16's subnormals.  kind None: the exact values, unchanged."""
+    return _with_window(lambda: varlen_ref.forward(q, k, v, cu_q, cu_k, True, scale, kind), causal, window)
 
 
 def backward(dout, q, k, v, cu_q, cu_k, causal: bool = False, window=(-1, -1), scale=None):
