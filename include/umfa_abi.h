@@ -643,6 +643,37 @@ mfa_error_t umfa_varlen_kvcache_attention_rope_forward_stream(
     const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
     bool rotary_interleaved);
 
+/* MI355X extra: sliding-window attention over a 16-bit paged or static KV cache (flash_attn_with_kvcache's window_size).  The
+ * arguments are umfa_kvcache_attention_rope_forward_stream's followed by the window; rotary_cos == rotary_sin == NULL means no rotary
+ * (the rotary arguments are then ignored), and cache_fp8 == true or a descale argument is MFA_ERROR_INVALID_ARGS (fp8 caches with a
+ * window are not built).
+ *   With L_k = clamp(cache_seqlens[b]) + seqlen_new, clamped as in umfa_kvcache_attention_forward_stream, and off = L_k - seqlen_q, query
+ *   token i of sequence b sees key j iff j < L_k, j's page entry lies in [0, num_pages) and i + off - window_left <= j <= i + off +
+ *   window_right.  A side given as -1 is unbounded; a value below -1 is MFA_ERROR_INVALID_ARGS.  causal sets window_right = 0 (and, with
+ *   rotary, places the query positions as in the rotary entry: the window does not).  A row that sees no key gives O = 0 exactly and
+ *   LSE = -inf.  window_left >= capacity (max_pages_per_seq * page_size; static: page_size) and window_right >= seqlen_q cannot bind and
+ *   count as unbounded.  A window with both sides unbounded -- or the left unbounded, the right 0 and causal set -- launches the
+ *   unwindowed kernels of the plain / rotary entry, bit for bit; every other window takes the banded kernel: each workgroup sweeps only
+ *   the 128-key steps its rows' band touches, and split-KV parts divide those steps, so the cost follows the band and not the context.
+ *   num_splits 0 chooses the part count from the band's length.  Block-table entries of pages wholly below the band are never read.
+ *   The capacity must be below 2^30 (MFA_ERROR_INVALID_ARGS otherwise).  The append, the clamps, the memory-safety rules, stream
+ *   capture (after a warm-up call) and the error codes are the plain and rotary entries'.  In-stream, never synchronising. */
+mfa_error_t umfa_kvcache_attention_window_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                         void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                         const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                         const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                         int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                         uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                         uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                                         uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                         int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                         int32_t num_splits, bool cache_fp8, const float* k_descale,
+                                                         const int64_t* k_descale_strides, const float* v_descale,
+                                                         const int64_t* v_descale_strides, const void* rotary_cos, const void* rotary_sin,
+                                                         int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro,
+                                                         uint32_t rotary_dim, bool rotary_interleaved, int32_t window_left,
+                                                         int32_t window_right);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

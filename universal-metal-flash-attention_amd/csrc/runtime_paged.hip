@@ -1,6 +1,7 @@
 // runtime_paged.hip -- the C ABI of KV-cache attention for inference (include/umfa_abi.h): umfa_kvcache_attention_forward_stream, over an
 // fp8 (e4m3fn) cache with per-(batch, KV head) descales (fa_paged_fp8.h) umfa_kvcache_attention_fp8_forward_stream, and with the rotary
-// embedding of q and k_new fused into the append launch (fa_paged_rope.h) umfa_kvcache_attention_rope_forward_stream.
+// embedding of q and k_new fused into the append launch (fa_paged_rope.h) umfa_kvcache_attention_rope_forward_stream, and with a sliding
+// window over a 16-bit cache (fa_paged_window.h) umfa_kvcache_attention_window_forward_stream.
 // In-stream, never synchronising: cache_seqlens and the block table stay on the device (the kernels read them when they run), so a
 // captured graph follows their contents on replay.  Launch order on the stream: the append of k_new / v_new (when given), the attention,
 // and with split-KV the fold.  Split partials come from the stream's pooled workspace (a capture that would have to grow it returns
@@ -10,6 +11,7 @@
 #include "runtime_internal.h"
 #include "fa_paged_fp8.h"
 #include "fa_paged_rope.h"
+#include "fa_paged_window.h"
 
 using namespace umfa;
 using namespace umfa_rt;
@@ -48,20 +50,43 @@ uint32_t paged_auto_splits(const PagedParams& p, int ncu) {
     return (uint32_t)(n < 64 ? n : 64);
 }
 
+// the band of a window call, normalised by the entry: each side a bound that binds or PAGED_WIN_OPEN
+struct WindowArgs {
+    int left, right;
+};
+
+// paged_auto_splits' rule with the length capped by the band instead of the capacity: a workgroup visits the steps of at most
+// left + right + Sq keys (an open side: the capacity), plus one step for a band that straddles a step boundary
+uint32_t paged_window_auto_splits(const PagedParams& p, const WindowArgs& w, int ncu) {
+    const uint64_t items = (uint64_t)p.B * p.Hkv * p.nrb;
+    const uint64_t slots = (uint64_t)ncu * (p.D == 128 ? 1 : 2);
+    if (items >= slots) return 1;
+    uint64_t n = (slots + items - 1) / items;
+    const uint64_t cap = (uint64_t)p.max_pages * p.page_size;
+    const uint64_t band = (w.left == PAGED_WIN_OPEN ? cap : (uint64_t)w.left) + (w.right == PAGED_WIN_OPEN ? cap : (uint64_t)w.right) + p.Sq;
+    const uint64_t steps = ((band < cap ? band : cap) + 127) / 128 + 1;
+    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
+    n = n < by_len ? n : by_len;
+    return (uint32_t)(n < 64 ? n : 64);
+}
+
 }  // namespace
 
 namespace {
 
 // every entry: fp8 = the cache is e4m3fn with the descales in f8 (cache strides in bytes), else 16-bit in input_precision; rope != NULL:
-// the fused pre-pass (fa_paged_rope.h) stands in for the append and the attention reads its q image
+// the fused pre-pass (fa_paged_rope.h) stands in for the append and the attention reads its q image; win != NULL (16-bit caches): the
+// banded kernel (fa_paged_window.h) stands in for the attention, `causal` then only places the rotary positions of q
 mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache,
                             const int64_t* k_cache_strides, void* v_cache, const int64_t* v_cache_strides, const void* k_new,
                             const int64_t* k_new_strides, const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
                             int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch, uint32_t seqlen_q,
                             uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size,
                             uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision,
-                            void* out, int32_t out_precision, float* lse, int32_t num_splits, bool fp8, PagedFp8Params f8, const RopeArgs* rope = nullptr) {
+                            void* out, int32_t out_precision, float* lse, int32_t num_splits, bool fp8, PagedFp8Params f8, const RopeArgs* rope = nullptr,
+                            const WindowArgs* win = nullptr) {
     Context* ctx = as_ctx(context);
+    if (win && fp8) return MFA_ERROR_INVALID_ARGS;
     if (rope && (!seqlen_new || !rope->cos || !rope->sin || rope->table_f32 < 0))
         return MFA_ERROR_INVALID_ARGS;
     if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !k_cache_strides || !v_cache_strides) return MFA_ERROR_INVALID_ARGS;
@@ -101,13 +126,21 @@ mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, 
     p.ks4 = R <= 32 ? 1 : 0;
     p.nrb = p.ks4 ? 1u : (uint32_t)((R + 127) / 128);
     p.nsplit = 1;
-    auto supported = [&]() { return fp8 ? paged_fp8_supported(f8) : paged_supported(p); };
+    auto supported = [&]() {
+        return fp8 ? paged_fp8_supported(f8) : win ? paged_window_supported(PagedWindowParams{p, win->left, win->right}) : paged_supported(p);
+    };
+    auto attend = [&](const char** nm) {  // (p as it stands at the launch: the rotary path has pointed p.q at its image by then)
+        if (win) return launch_fwd_16_paged_window(PagedWindowParams{p, win->left, win->right}, (hipStream_t)stream, nm);
+        return fp8 ? launch_fwd_16_paged_fp8(f8, (hipStream_t)stream, nm) : launch_fwd_16_paged(p, (hipStream_t)stream, nm);
+    };
     if (!supported() || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
     const char* name = "none";
     std::lock_guard<std::mutex> lock(ctx->mu);
     const int dev = stream_device((hipStream_t)stream);
     DeviceGuard guard(dev);
-    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : paged_auto_splits(p, paged_cu_count(dev));
+    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256)
+               : win          ? paged_window_auto_splits(p, *win, paged_cu_count(dev))
+                              : paged_auto_splits(p, paged_cu_count(dev));
     if (!supported()) return MFA_ERROR_INVALID_ARGS;
     if (rope) {
         // one block of the pooled workspace: the rotated q image, then (split) the partials; every check and the allocation come before
@@ -129,7 +162,7 @@ mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, 
         if (const hipError_t e = launch_paged_rope(r, (hipStream_t)stream); e != hipSuccess) return rc_paged(e);
         p.q = r.qimg;
         p.qsb = (int64_t)seqlen_q * num_heads * head_dim; p.qst = (int64_t)num_heads * head_dim; p.qsh = head_dim;
-        const hipError_t e = fp8 ? launch_fwd_16_paged_fp8(f8, (hipStream_t)stream, &name) : launch_fwd_16_paged(p, (hipStream_t)stream, &name);
+        const hipError_t e = attend(&name);
         ctx->last_kernel = name;
         return rc_paged(e);
     }
@@ -143,7 +176,7 @@ mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, 
         const hipError_t e = fp8 ? launch_paged_fp8_append(f8, (hipStream_t)stream) : launch_paged_append(p, (hipStream_t)stream);
         if (e != hipSuccess) return rc_paged(e);
     }
-    const hipError_t e = fp8 ? launch_fwd_16_paged_fp8(f8, (hipStream_t)stream, &name) : launch_fwd_16_paged(p, (hipStream_t)stream, &name);
+    const hipError_t e = attend(&name);
     ctx->last_kernel = name;
     return rc_paged(e);
 }
@@ -216,4 +249,41 @@ mfa_error_t umfa_kvcache_attention_rope_forward_stream(mfa_context_t context, vo
                            v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
                            num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
                            out_precision, lse, num_splits, cache_fp8, f8, &rope);
+}
+
+mfa_error_t umfa_kvcache_attention_window_forward_stream(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides,
+                                                         void* k_cache, const int64_t* k_cache_strides, void* v_cache,
+                                                         const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides,
+                                                         const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
+                                                         int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t batch,
+                                                         uint32_t seqlen_q, uint32_t seqlen_new, uint32_t num_heads, uint32_t num_kv_heads,
+                                                         uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
+                                                         uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+                                                         int32_t input_precision, void* out, int32_t out_precision, float* lse,
+                                                         int32_t num_splits, bool cache_fp8, const float* k_descale,
+                                                         const int64_t* k_descale_strides, const float* v_descale,
+                                                         const int64_t* v_descale_strides, const void* rotary_cos, const void* rotary_sin,
+                                                         int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro,
+                                                         uint32_t rotary_dim, bool rotary_interleaved, int32_t window_left,
+                                                         int32_t window_right) {
+    if (cache_fp8 || k_descale || v_descale || k_descale_strides || v_descale_strides) return MFA_ERROR_INVALID_ARGS;
+    if (window_left < -1 || window_right < -1) return MFA_ERROR_INVALID_ARGS;
+    if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
+    // the window, normalised once: causal is right = 0; a side that cannot bind (left >= capacity, right >= Sq) is open
+    const uint64_t cap = block_table ? (uint64_t)max_pages_per_seq * page_size : (uint64_t)page_size;
+    if (cap >= (1ull << 30)) return MFA_ERROR_INVALID_ARGS;
+    if (causal) window_right = 0;
+    WindowArgs w;
+    w.left = window_left < 0 || (uint64_t)window_left >= cap ? PAGED_WIN_OPEN : window_left;
+    w.right = window_right < 0 || (uint32_t)window_right >= seqlen_q ? PAGED_WIN_OPEN : window_right;
+    // a window that bounds nothing (or only as causal does): the unwindowed kernels, unchanged
+    const bool plain = w.left == PAGED_WIN_OPEN && (w.right == PAGED_WIN_OPEN || (causal && w.right == 0));
+    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
+    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    PagedFp8Params f8;
+    memset(&f8, 0, sizeof(f8));
+    return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,
+                           v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
+                           num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
+                           out_precision, lse, num_splits, false, f8, rotary_cos ? &rope : nullptr, plain ? nullptr : &w);
 }

@@ -153,9 +153,9 @@ _UNSUPPORTED = {"cache_batch_idx": None, "cache_leftpad": None, "window_size": (
                 "softcap": 0.0, "alibi_slopes": None}
 
 
-def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table, fp8=False):
+def _check(q, k_cache, v_cache, k, v, cache_seqlens, block_table, fp8=False, fn="kvcache_attention"):
     def bad(msg):
-        raise ValueError(f"kvcache_attention: {msg}")
+        raise ValueError(f"{fn}: {msg}")
 
     for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
         ok = (torch.float8_e4m3fn,) if fp8 and name != "q" else _DTYPES
@@ -261,6 +261,7 @@ def kvcache_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     rotary_interleaved: pairs (2i, 2i + 1) instead of (i, i + rotary_dim / 2); ignored without tables.  k / v are required; a position
     at or past seqlen_ro takes the last table row.
     cache_batch_idx / cache_leftpad / window_size / softcap / alibi_slopes are accepted at their defaults only.
+    A sliding window over the cache is a function of its own, kvcache_window_attention.
     Raises ValueError outside the kernels' scope (see the module docstring)."""
     for name, val in unsupported.items():
         if name not in _UNSUPPORTED:

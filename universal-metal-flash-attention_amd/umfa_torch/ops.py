@@ -692,6 +692,28 @@ def kvcache_attention_rope_forward(q, k_cache, v_cache, cache_seqlens, rotary_co
                             v_new, scale, causal, num_splits, out_dtype, out, lse)
 
 
+def kvcache_attention_window_forward(q, k_cache, v_cache, cache_seqlens, block_table=None, k_new=None, v_new=None, *, scale: float,
+                                     causal: bool = False, window=(-1, -1), num_splits: int = 0, rotary_cos=None, rotary_sin=None,
+                                     rotary_interleaved: bool = False, out_dtype=None, out=None, lse=None, cache_fp8: bool = False):
+    """kvcache_attention_forward with a sliding window (umfa_kvcache_attention_window_forward_stream): window = (left, right),
+    flash-attention's window_size -- with off = L_k - Sq, query token i sees keys i + off - left .. i + off + right of the L_k the plain
+    call covers; -1 is unbounded, causal sets right = 0.  16-bit caches (cache_fp8 is the entry's flag and is refused).  With rotary_cos
+    / rotary_sin the rotary embedding is fused into the append launch as in kvcache_attention_rope_forward (new tokens required).  The
+    entry normalises the window; one that bounds nothing runs the unwindowed kernels, bit for bit."""
+    left, right = (int(x) for x in window)
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError("kvcache_attention_window_forward: rotary_cos and rotary_sin must be given together")
+    if rotary_cos is not None:
+        if k_new is None or v_new is None or k_new.shape[1] == 0:
+            raise ValueError("kvcache_attention_window_forward: rotary needs new tokens (k_new / v_new)")
+        rope = _rope_args("kvcache_attention_window_forward", q, rotary_cos, rotary_sin, rotary_interleaved)
+    else:
+        rope = (None, None, _PREC[q.dtype], 0, 0, 0, False)
+    extra = (bool(cache_fp8), None, None, None, None, *rope, left, right)
+    return _kvcache_forward(_lib.umfa_kvcache_attention_window_forward_stream, extra, q, k_cache, v_cache, cache_seqlens, block_table, k_new,
+                            v_new, scale, causal, num_splits, out_dtype, out, lse)
+
+
 def _varlen_kvcache_forward(name, entry, extra, q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale,
                             causal, num_splits, out_dtype, out=None, lse=None):
     """the call both packed KV-cache entries share; name: the public wrapper (for messages); extra: the arguments behind num_splits (the
