@@ -643,6 +643,44 @@ mfa_error_t umfa_varlen_kvcache_attention_rope_forward_stream(
     const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
     bool rotary_interleaved);
 
+/* MI355X extra: umfa_varlen_kvcache_attention_forward_stream over an fp8 KV cache -- packed variable-length queries over the e4m3fn
+ * paged or static cache of umfa_kvcache_attention_fp8_forward_stream, with the quantising packed append and, optionally, the fused
+ * rotary embedding.  The arguments are umfa_varlen_kvcache_attention_forward_stream's, then the four descale arguments of the fp8 entry,
+ * then the rotary arguments of umfa_varlen_kvcache_attention_rope_forward_stream; rotary_cos == rotary_sin == NULL means no rotary (the
+ * other rotary arguments are then ignored); exactly one of them NULL is MFA_ERROR_INVALID_ARGS.  The contract is the union of the two:
+ *   Layouts and clamps: umfa_varlen_kvcache_attention_forward_stream's, word for word -- q / cu_seqlens_q / the caches / the table / the
+ *   lengths, L_k,b = min(L0_b + L_q,b, cap), bottom-right causal per sequence, O = 0 / LSE = -inf for a row that sees no key, rows no
+ *   sequence covers left unwritten, the work items and the item-list pre-pass, and every clamp that makes any contents of
+ *   cu_seqlens_q, cache_seqlens and the block table memory-safe.
+ *   Bytes and arithmetic: umfa_kvcache_attention_fp8_forward_stream's -- k_cache / v_cache hold OCP e4m3fn bytes, both of them; a byte
+ *   stands for e4m3fn(byte) * descale[b, h_kv] with b the SEQUENCE (a page shared by two sequences decodes under each one's own
+ *   descale); k_descale / v_descale are DEVICE fp32 at descale[b * strides[0] + h_kv * strides[1]], element strides >= 0 that may be 0,
+ *   never read by the host, so a captured graph follows their contents on replay; the expansions to the 16-bit operand types are exact
+ *   and the arithmetic is the 16-bit entry's.  Cache strides are in elements = bytes, multiples of 16, bases 16-byte aligned.
+ *   Append (has_new): packed row t of sequence b is stored at cache position L0_b + (t - cu[b]) as
+ *   e4m3fn_rne(clamp(fp32(x) / descale[b, h_kv], -448, +448)) -- IEEE fp32 division, the clamp before the conversion; rows no sequence
+ *   covers, rows past the capacity and rows of pages the table does not hold are dropped.
+ *   Rotary (needs has_new): umfa_kvcache_attention_rope_forward_stream's rule at positions L0_b + (t - cu[b]) for the new keys and, when
+ *   causal, the queries; every query row of sequence b at L0_b when not causal.  The rotated key is rounded once to the operand type,
+ *   then quantised.  ONE pre-pass launch replaces the append launch; the result equals, in every bit of out, lse and both pools, this
+ *   entry without rotary called on q and k_new rotated that way and rounded to the operand type.
+ *   With every L_q,b equal the result equals umfa_kvcache_attention_fp8_forward_stream's (with rotary:
+ *   umfa_kvcache_attention_rope_forward_stream's with cache_fp8) bit for bit at the same num_splits.
+ *   The q image, the item list and the split partials share the stream's pooled workspace: valid under stream capture after a warm-up
+ *   call, a capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION and launches nothing.  Never synchronises;
+ *   umfa_varlen_kvcache_item_counts reads this call's tally too.  Scope: fp16 / bf16 q and new tokens, head_dim 64 / 128, page_size a
+ *   multiple of 16, no window; anything else MFA_ERROR_INVALID_ARGS -- no fall-back. */
+mfa_error_t umfa_varlen_kvcache_attention_fp8_forward_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache, const int64_t* k_cache_strides,
+    void* v_cache, const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides, const void* v_new,
+    const int64_t* v_new_strides, const int32_t* block_table, int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+    uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads, uint32_t num_kv_heads,
+    uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+    int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const float* k_descale,
+    const int64_t* k_descale_strides, const float* v_descale, const int64_t* v_descale_strides, const void* rotary_cos,
+    const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
+    bool rotary_interleaved);
+
 /* MI355X extra: sliding-window attention over a 16-bit paged or static KV cache (flash_attn_with_kvcache's window_size).  The
  * arguments are umfa_kvcache_attention_rope_forward_stream's followed by the window; rotary_cos == rotary_sin == NULL means no rotary
  * (the rotary arguments are then ignored), and cache_fp8 == true or a descale argument is MFA_ERROR_INVALID_ARGS (fp8 caches with a

@@ -521,7 +521,14 @@ hipError_t launch_paged_varlen_append(const PagedVarlenParams& v, hipStream_t st
     return hipGetLastError();
 }
 
-static hipError_t launch_paged_varlen_fold(const PagedVarlenParams& v, hipStream_t stream) {
+// the item-list pre-pass alone (fa_fwd_16_paged_varlen_fp8.hip launches it in front of its own forward)
+hipError_t launch_paged_varlen_items(const PagedVarlenParams& v, hipStream_t stream) {
+    hipLaunchKernelGGL(fa_paged_varlen_items_kernel, dim3(1), dim3(256), 0, stream, v);
+    return hipGetLastError();
+}
+
+// the split-KV fold alone (v.p.nsplit parts in v.p.part)
+hipError_t launch_paged_varlen_fold(const PagedVarlenParams& v, hipStream_t stream) {
     const uint64_t rows = (uint64_t)v.Tq * v.p.H, rpb = 256 / (v.p.D / 4);
     const dim3 grid((uint32_t)((rows + rpb - 1) / rpb));
     if (v.p.out_prec == P_FP32)
@@ -572,8 +579,7 @@ hipError_t launch_fwd_16_paged_varlen(const PagedVarlenParams& v, hipStream_t st
     const bool bf = p.in_prec == P_BF16;
     *name = names[bf][p.D == 128][p.causal != 0][p.nsplit > 1];
     if (v.n_items == 0) return hipSuccess;  // (T_q = 0 or max_seqlen_q = 0: no row exists)
-    hipLaunchKernelGGL(fa_paged_varlen_items_kernel, dim3(1), dim3(256), 0, stream, v);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (hipError_t e = launch_paged_varlen_items(v, stream); e != hipSuccess) return e;
     if (p.D == 64) return bf ? launch_fwd16_paged_varlen_d<__bf16, 64>(v, stream) : launch_fwd16_paged_varlen_d<_Float16, 64>(v, stream);
     return bf ? launch_fwd16_paged_varlen_d<__bf16, 128>(v, stream) : launch_fwd16_paged_varlen_d<_Float16, 128>(v, stream);
 }

@@ -42,6 +42,8 @@ bool paged_varlen_supported(const PagedVarlenParams& v);
 uint32_t paged_varlen_item_bound(const PagedVarlenParams& v);  // n_items for v's T_q, B, max_seqlen_q, H, H_kv
 hipError_t launch_paged_varlen_append(const PagedVarlenParams& v, hipStream_t stream);
 hipError_t launch_fwd_16_paged_varlen(const PagedVarlenParams& v, hipStream_t stream, const char** name);  // items, forward, fold
+hipError_t launch_paged_varlen_items(const PagedVarlenParams& v, hipStream_t stream);  // the item-list pre-pass alone
+hipError_t launch_paged_varlen_fold(const PagedVarlenParams& v, hipStream_t stream);   // the split-KV fold alone (p.nsplit parts in p.part)
 
 namespace {
 

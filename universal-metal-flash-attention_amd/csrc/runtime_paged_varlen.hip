@@ -1,6 +1,7 @@
 // runtime_paged_varlen.hip -- the C ABI of packed variable-length queries over a paged / static KV cache (include/umfa_abi.h):
-// umfa_varlen_kvcache_attention_forward_stream and, with the rotary embedding of q and k_new fused into the append launch
-// (fa_paged_rope.h), umfa_varlen_kvcache_attention_rope_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
+// umfa_varlen_kvcache_attention_forward_stream, with the rotary embedding of q and k_new fused into the append launch
+// (fa_paged_rope.h) umfa_varlen_kvcache_attention_rope_forward_stream, and over an fp8 (e4m3fn) cache with per-(sequence, KV head)
+// descales, with or without rotary (fa_paged_varlen_fp8.h), umfa_varlen_kvcache_attention_fp8_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
 // the device, so a captured graph follows their contents on replay.  Launch order on the stream: the packed append of k_new / v_new
 // (when given), the item-list pre-pass, the attention, and with split-KV the fold.  The item list and the split partials come from the
 // stream's pooled workspace (a capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION: warm up first).  Anything
@@ -10,6 +11,7 @@
 #include "runtime_internal.h"
 #include "fa_paged_varlen.h"
 #include "fa_paged_rope.h"
+#include "fa_paged_varlen_fp8.h"
 
 using namespace umfa;
 using namespace umfa_rt;
@@ -50,7 +52,8 @@ constexpr size_t PV_HDR_B = 256;  // the tally's words at the front of the works
 
 namespace {
 
-// both entries; rope != NULL: the fused pre-pass (fa_paged_rope.h) stands in for the packed append and the attention reads its q image
+// every entry; rope != NULL: the fused pre-pass (fa_paged_rope.h) stands in for the packed append and the attention reads its q image;
+// f8 != NULL: the cache is e4m3fn with f8's descales (cache strides in bytes) and the kernels are fa_fwd_16_paged_varlen_fp8.hip's
 mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache,
                                    const int64_t* k_cache_strides, void* v_cache, const int64_t* v_cache_strides, const void* k_new,
                                    const int64_t* k_new_strides, const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
@@ -58,7 +61,8 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
                                    uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads,
                                    uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
                                    uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision, void* out,
-                                   int32_t out_precision, float* lse, int32_t num_splits, const RopeArgs* rope) {
+                                   int32_t out_precision, float* lse, int32_t num_splits, const RopeArgs* rope,
+                                   const PagedVarlenFp8Params* f8 = nullptr) {
     Context* ctx = as_ctx(context);
     if (rope && (!has_new || !rope->cos || !rope->sin || rope->table_f32 < 0))
         return MFA_ERROR_INVALID_ARGS;
@@ -71,7 +75,10 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
     if (has_new && (!k_new || !v_new || !k_new_strides || !v_new_strides)) return MFA_ERROR_INVALID_ARGS;
     if (block_table && block_table_stride < (int64_t)max_pages_per_seq) return MFA_ERROR_INVALID_ARGS;
     if (max_seqlen_q > total_q) return MFA_ERROR_INVALID_ARGS;
-    PagedVarlenParams v;
+    PagedVarlenFp8Params f;
+    memset(&f, 0, sizeof(f));
+    if (f8) f = *f8;
+    PagedVarlenParams& v = f.v;
     memset(&v, 0, sizeof(v));
     PagedParams& p = v.p;
     p.q = q; p.kc = k_cache; p.vc = v_cache; p.bt = block_table; p.seqlens = cache_seqlens;
@@ -100,13 +107,14 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
     if (num_kv_heads == 0 || num_heads % num_kv_heads) return MFA_ERROR_INVALID_ARGS;
     p.nsplit = 1;
     v.n_items = paged_varlen_item_bound(v);
-    if (!paged_varlen_supported(v) || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
+    auto supported = [&]() { return f8 ? paged_varlen_fp8_supported(f) : paged_varlen_supported(v); };
+    if (!supported() || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
     const char* name = "none";
     std::lock_guard<std::mutex> lock(ctx->mu);
     const int dev = stream_device((hipStream_t)stream);
     DeviceGuard guard(dev);
     p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : pv_auto_splits(v, pv_cu_count(dev));
-    if (!paged_varlen_supported(v)) return MFA_ERROR_INVALID_ARGS;
+    if (!supported()) return MFA_ERROR_INVALID_ARGS;
     PagedRopeParams r;
     memset(&r, 0, sizeof(r));
     if (rope) {
@@ -131,15 +139,24 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
     }
     if (rope) {
         if (total_q) {
-            if (!paged_rope_supported(r)) return MFA_ERROR_INVALID_ARGS;
-            if (const hipError_t e = launch_paged_rope(r, (hipStream_t)stream); e != hipSuccess) return rc_pv(e);
+            hipError_t e;
+            if (f8) {
+                const PagedVarlenFp8RopeParams r8 = {f, r.cos, r.sin, r.qimg, r.rstride, r.seqlen_ro, r.rdim, r.interleaved, r.table_f32};
+                if (!paged_varlen_fp8_rope_supported(r8)) return MFA_ERROR_INVALID_ARGS;
+                e = launch_paged_varlen_fp8_rope(r8, (hipStream_t)stream);
+            } else {
+                if (!paged_rope_supported(r)) return MFA_ERROR_INVALID_ARGS;
+                e = launch_paged_rope(r, (hipStream_t)stream);
+            }
+            if (e != hipSuccess) return rc_pv(e);
             p.q = r.qimg;
             p.qst = (int64_t)num_heads * head_dim; p.qsh = head_dim;
         }
     } else if (has_new) {
-        if (const hipError_t e = launch_paged_varlen_append(v, (hipStream_t)stream); e != hipSuccess) return rc_pv(e);
+        const hipError_t e = f8 ? launch_paged_varlen_fp8_append(f, (hipStream_t)stream) : launch_paged_varlen_append(v, (hipStream_t)stream);
+        if (e != hipSuccess) return rc_pv(e);
     }
-    const hipError_t e = launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
+    const hipError_t e = f8 ? launch_fwd_16_paged_varlen_fp8(f, (hipStream_t)stream, &name) : launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
     ctx->last_kernel = name;
     return rc_pv(e);
 }
@@ -177,6 +194,31 @@ mfa_error_t umfa_varlen_kvcache_attention_rope_forward_stream(
                                   v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
                                   cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
                                   softmax_scale, causal, input_precision, out, out_precision, lse, num_splits, &rope);
+}
+
+mfa_error_t umfa_varlen_kvcache_attention_fp8_forward_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache, const int64_t* k_cache_strides,
+    void* v_cache, const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides, const void* v_new,
+    const int64_t* v_new_strides, const int32_t* block_table, int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+    uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads, uint32_t num_kv_heads,
+    uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+    int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const float* k_descale,
+    const int64_t* k_descale_strides, const float* v_descale, const int64_t* v_descale_strides, const void* rotary_cos,
+    const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
+    bool rotary_interleaved) {
+    if (!k_descale || !v_descale || !k_descale_strides || !v_descale_strides) return MFA_ERROR_INVALID_ARGS;
+    if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
+    PagedVarlenFp8Params f8;
+    memset(&f8, 0, sizeof(f8));
+    f8.kd = k_descale; f8.kdb = k_descale_strides[0]; f8.kdh = k_descale_strides[1];
+    f8.vd = v_descale; f8.vdb = v_descale_strides[0]; f8.vdh = v_descale_strides[1];
+    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
+    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
+                                  v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
+                                  cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
+                                  softmax_scale, causal, input_precision, out, out_precision, lse, num_splits, rotary_cos ? &rope : nullptr,
+                                  &f8);
 }
 
 // debug: the tally of the last umfa_varlen_kvcache_attention_forward_stream call on `stream` (nothing else may have used the stream's

@@ -210,6 +210,11 @@ def _load_library(path: str | None = None) -> ctypes.CDLL:
         sig("umfa_varlen_kvcache_attention_rope_forward_stream", mfa_error_t,
             [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,
              _u32, _u32, _u32, _vp, _b, _u32, _u32, _u16, _u32, _u32, _u32, _f32, _b, _i32, _vp, _i32, _vp, _i32] + _ROPE)
+        if path is None or hasattr(lib, "umfa_varlen_kvcache_attention_fp8_forward_stream"):  # packed queries over an fp8 cache (include/umfa_abi.h)
+            sig("umfa_varlen_kvcache_attention_fp8_forward_stream", mfa_error_t,
+                [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,
+                 _u32, _u32, _u32, _vp, _b, _u32, _u32, _u16, _u32, _u32, _u32, _f32, _b, _i32, _vp, _i32, _vp, _i32, _vp, _i64p, _vp, _i64p]
+                + _ROPE)
         if path is None or hasattr(lib, "umfa_kvcache_attention_window_forward_stream"):  # ... with a sliding window (include/umfa_abi.h)
             sig("umfa_kvcache_attention_window_forward_stream", mfa_error_t,
                 [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,

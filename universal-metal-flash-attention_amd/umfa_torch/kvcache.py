@@ -228,19 +228,21 @@ def _check_rotary(fn, q, k, new_tokens, rotary_cos, rotary_sin):
     return True
 
 
-def _descale(d, q, Hkv, name):
+def _descale(d, q, Hkv, name, B=None, fn="kvcache_attention"):
     """a descale argument as the device fp32 tensor the op takes: None = 1.0, a Python number becomes a one-element tensor (a fill on
-    the device, no synchronisation), a tensor must be device fp32 and broadcast to [B, H_kv]"""
-    if d is None or isinstance(d, (int, float)):
+    the device, no synchronisation), a tensor must be device fp32 and broadcast to [B, H_kv] (B: q's batch, or the packed call's
+    sequence count)"""
+    B = q.shape[0] if B is None else B
+    if d is None or (isinstance(d, (int, float)) and not isinstance(d, bool)):
         return torch.full((1,), 1.0 if d is None else float(d), dtype=torch.float32, device=q.device)
     if not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.device != q.device or d.dim() > 2:
-        raise ValueError(f"kvcache_attention: {name} must be a float or an fp32 tensor on q's device that broadcasts to [batch, num_kv_heads]")
+        raise ValueError(f"{fn}: {name} must be a float or an fp32 tensor on q's device that broadcasts to [batch, num_kv_heads]")
     try:
-        torch.broadcast_shapes(tuple(d.shape), (q.shape[0], Hkv))
+        torch.broadcast_shapes(tuple(d.shape), (B, Hkv))
     except RuntimeError:
-        raise ValueError(f"kvcache_attention: {name} {tuple(d.shape)} does not broadcast to [{q.shape[0]}, {Hkv}]") from None
-    if d.dim() == 2 and (d.shape[0] > q.shape[0] or d.shape[1] > Hkv):
-        raise ValueError(f"kvcache_attention: {name} {tuple(d.shape)} does not broadcast to [{q.shape[0]}, {Hkv}]")
+        raise ValueError(f"{fn}: {name} {tuple(d.shape)} does not broadcast to [{B}, {Hkv}]") from None
+    if d.dim() == 2 and (d.shape[0] > B or d.shape[1] > Hkv):
+        raise ValueError(f"{fn}: {name} {tuple(d.shape)} does not broadcast to [{B}, {Hkv}]")
     return d
 
 

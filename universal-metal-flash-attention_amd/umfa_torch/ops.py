@@ -716,8 +716,8 @@ def kvcache_attention_window_forward(q, k_cache, v_cache, cache_seqlens, block_t
 
 def _varlen_kvcache_forward(name, entry, extra, q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale,
                             causal, num_splits, out_dtype, out=None, lse=None):
-    """the call both packed KV-cache entries share; name: the public wrapper (for messages); extra: the arguments behind num_splits (the
-    rotary entry's tail); out / lse: the caller's buffers (_out_buffers)"""
+    """the call the packed KV-cache entries share; name: the public wrapper (for messages); extra: the arguments behind num_splits (the
+    rotary entry's tail, the fp8 entry's descales and rotary tail); out / lse: the caller's buffers (_out_buffers)"""
     Tq, H, D = q.shape
     B = cu_seqlens_q.numel() - 1
     if cu_seqlens_q.dim() != 1 or B < 1 or cache_seqlens.shape != (B,) or cu_seqlens_q.stride(0) != 1 or (B > 1 and cache_seqlens.stride(0) != 1) \
@@ -772,8 +772,38 @@ def varlen_kvcache_attention_rope_forward(q, k_cache, v_cache, cu_seqlens_q, max
                                    max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype, out, lse)
 
 
+def varlen_kvcache_attention_fp8_forward(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, k_descale, v_descale,
+                                         block_table=None, k_new=None, v_new=None, *, scale: float, causal: bool = False, num_splits: int = 0,
+                                         rotary_cos=None, rotary_sin=None, rotary_interleaved: bool = False, out_dtype=None, out=None,
+                                         lse=None):
+    """varlen_kvcache_attention_forward over an fp8 cache (umfa_varlen_kvcache_attention_fp8_forward_stream): k_cache / v_cache
+    torch.float8_e4m3fn in the same layouts (strides multiples of 16 bytes), q / k_new / v_new fp16 or bf16 and packed by cu_seqlens_q.
+    k_descale / v_descale: device fp32, a scalar, [H_kv], [B, 1] or [B, H_kv] with B the sequences; a cache byte stands for
+    e4m3fn(byte) * descale[b, h_kv], and packed row t of sequence b is stored as e4m3fn(clamp(x / descale[b, h_kv], -448, 448)).  With
+    rotary_cos / rotary_sin (new tokens required) the rotary embedding is fused into the quantising append launch as in
+    varlen_kvcache_attention_rope_forward: the rotated key is rounded to q's dtype, then quantised.  The descales are never read back.
+    out / lse: optional dense buffers [T_q, H, D] / fp32 [H, T_q] to write into (rows no sequence covers stay as they were)."""
+    name = "varlen_kvcache_attention_fp8_forward"
+    if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{name}: k_cache and v_cache must both be torch.float8_e4m3fn (got {k_cache.dtype}, {v_cache.dtype})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{name}: q must be fp16 or bf16 (got {q.dtype})")
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError(f"{name}: rotary_cos and rotary_sin must be given together")
+    if rotary_cos is not None:
+        if k_new is None or v_new is None:
+            raise ValueError(f"{name}: rotary needs new tokens (k_new / v_new)")
+        rope = _rope_args(name, q, rotary_cos, rotary_sin, rotary_interleaved)
+    else:
+        rope = (None, None, _PREC[q.dtype], 0, 0, 0, False)
+    B, Hkv = cu_seqlens_q.numel() - 1, k_cache.shape[2]
+    extra = (*_descale_arg(k_descale, B, Hkv, "k_descale"), *_descale_arg(v_descale, B, Hkv, "v_descale"), *rope)
+    return _varlen_kvcache_forward(name, _lib.umfa_varlen_kvcache_attention_fp8_forward_stream, extra, q, k_cache, v_cache, cu_seqlens_q,
+                                   max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype, out, lse)
+
+
 def varlen_kvcache_item_counts(device=None):
-    """(decode-form items, 128-row items) the last varlen_kvcache_attention_forward on torch's current stream ran, counted by the
+    """(decode-form items, 128-row items) the last varlen_kvcache_attention_forward (16-bit or fp8) on torch's current stream ran, counted by the
     kernel (umfa_varlen_kvcache_item_counts).  Debug: synchronises the stream."""
     stream = torch.cuda.current_stream(device).cuda_stream
     a, b = ctypes.c_uint32(), ctypes.c_uint32()
