@@ -2,58 +2,21 @@
 // cache (head_dim 64 / 128, causal or not, GQA), with the packed in-place append, the item-list pre-pass and the split-KV fold.
 // Semantics, layout, memory safety and the work distribution: fa_paged_varlen.h.
 //
-// The workgroup is fa_fwd_16_paged.hip's: 4 waves x 32 query rows, S^T = K Q^T, the rows of one (sequence, KV head) packed (row r is
-// query token r / g of query head hk g + r % g), a step of 128 keys of K and V staged by double-buffered LDS-DMA with one buffer
-// descriptor per 1-KiB piece based at the piece's own page, bf16 V converted to fp16 in LDS with the range rule's second sweep, and the
-// same split partial format.  What differs: a workgroup reads its (sequence, KV head, row block) from the item list instead of
-// deriving it from blockIdx, takes the sequence's query range from cu_seqlens_q, and decides between the decode form (ks4: R = g L_q
-// <= 32, the four waves split each step's keys and meet behind FWD16_EPI_HDR) and the 128-row form from its own L_q -- both forms run
-// in one launch.  q / O / LSE rows are cu[b] + token; the causal offset and the last visible key come from the item's L_q and L_k.
-// With every L_q equal the arithmetic, and its order, is that of fa_fwd16_paged_kernel: the results are bitwise the same.
+// The workgroup is fa_fwd_16_paged.hip's (the rows of one (sequence, KV head) packed, row r query token r / g of query head hk g + r % g;
+// double-buffered 128-key steps; the same split partial format) over the shared device pieces of fa_paged_device.h.  What differs: a
+// workgroup reads its (sequence, KV head, row block) from the item list instead of deriving it from blockIdx, takes the sequence's
+// query range from cu_seqlens_q, and decides between the decode form (ks4: R = g L_q <= 32) and the 128-row form from its own L_q --
+// both forms run in one launch.  q / O / LSE rows are cu[b] + token; the causal offset and the last visible key come from the item's
+// L_q and L_k.  With every L_q equal the arithmetic, and its order, is that of fa_fwd16_paged_kernel: the results are bitwise the same.
 #include <type_traits>
 
 #include "fa_paged_varlen.h"
-#include "fa_fwd_16_kernel.h"
+#include "fa_paged_device.h"
 #include "kernels.h"
 
 namespace umfa {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// lanes 0 .. 7 (and again 8 .. 15, ...): the physical page of 16-key group (lane & 7) of step s (keys 128 s .. 128 s + 127), -1 for an
-// entry outside the pool or a group at or past L_k.  One vector load per step, issued a step ahead of its use: read one entry at a time
-// with scalar loads, every piece and subtile waited for its own (page_size had no effect on the rate: all of it was these waits).
-__device__ __forceinline__ int paged_table(const PagedParams& p, uint32_t b, uint32_t Lk, uint32_t s, int lane) {
-    const uint32_t key = s * 128 + 16 * (uint32_t)(lane & 7);
-    return key < Lk ? paged_page(p, b, paged_lpage(p, key)) : -1;
-}
-
-// LDS-DMA of step s of one cache tensor, KV head at head_b bytes, into the 128-row swizzled image at lds_dst (pgv: paged_table of step
-// s): piece n (RPP rows) goes to lds_dst + n KiB, wave uw issues pieces uw, uw + 4, ...
-template <int DP>
-__device__ __forceinline__ void paged_dma_step(const PagedParams& p, const char* pool, int64_t page_b, int64_t head_b, uint32_t tst_b,
-                                               int pgv, uint32_t Lk, uint32_t s, unsigned lds_dst, int uw, int lane) {
-    constexpr int ROW_B = 2 * DP, NCH = DP / 8, RPP = 1024 / ROW_B, NP = 128 / RPP;
-    const int r = lane / NCH, c = lane % NCH;
-#pragma nounroll
-    for (int n0 = 0; n0 < NP; n0 += 4) {  // (one piece at a time: unrolled, the descriptors of all pieces ran out of scalar registers)
-        const int n = n0 + uw;
-        const uint32_t key0 = s * 128 + (uint32_t)(RPP * n);
-        const uint32_t lp = paged_lpage(p, key0);
-        const int pg = __builtin_amdgcn_readlane(pgv, (RPP * n) / 16);  // (the step's page of this piece's 16-key group: paged_table)
-        const uint32_t pstart = lp * p.page_size;
-        uint32_t nv = Lk > pstart ? Lk - pstart : 0u;
-        nv = nv < p.page_size ? nv : p.page_size;
-        const uint32_t bytes = pg >= 0 && nv ? (nv - 1) * tst_b + ROW_B : 0u;
-        const i32x4 srd = make_srd(pool + (int64_t)(pg >= 0 ? pg : 0) * page_b + head_b, bytes);
-        const int row = RPP * n + r;
-        const int voff = (int)((key0 - pstart + (uint32_t)r) * tst_b) + (d_off<DP>(row, c) - row * ROW_B);
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                     ::"s"(lds_dst + n * 1024), "v"(voff), "s"(srd) : "memory");
-    }
-}
 
 // row blocks of a sequence with R rows per KV head: one in the decode form, else 128 rows each
 __device__ __forceinline__ uint32_t varlen_blocks(uint32_t R) { return R == 0 ? 0u : (R <= 32 ? 1u : (R + 127) / 128); }
@@ -64,8 +27,8 @@ template <typename T, bool CAUSAL, int DP, typename OUT>
 __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarlenParams v) {
     const PagedParams& p = v.p;
     BWD16_GEO(DP);
+    (void)TILE_PIECES;
     constexpr int STAGE_B = 4 * TILE_BYTES;  // one step (128 keys) of K or of V
-    constexpr int NP = 128 / (1024 / ROW_B);  // pieces per step and tensor
     constexpr bool VCONV = std::is_same<T, __bf16>::value;
     constexpr bool SPLIT = std::is_same<OUT, void>::value;
     typedef Mma16<T> M;
@@ -112,17 +75,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
     const uint32_t nst = (Le + 127) / 128, per = (nst + p.nsplit - 1) / p.nsplit;
     const uint32_t s0 = part * per, s1 = s0 + per < nst ? s0 + per : nst;
 
-    V8 qf[NKS];
-    const T* qp = (const T*)p.q + (int64_t)(q0 + qi) * p.qst + (int64_t)h * p.qsh;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        if (rok) {
-            qf[ks] = *(const V8*)(qp + 16 * ks + 8 * hi);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[ks][j] = (T)0.0f;
-        }
-    }
+    typename Mma16<T>::V8 qf[NKS];
+    paged_load_q<T, DP>(qf, (const T*)p.q + (int64_t)(q0 + qi) * p.qst + (int64_t)h * p.qsh, rok, hi);
     const float c = p.scale * UMFA_LOG2E;
     const int lim = (int)qi + off;
     const uint32_t tst_k = (uint32_t)p.kst * 2, tst_v = (uint32_t)p.vst * 2;
@@ -130,27 +84,14 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((LDS_AS char*)smem));
     const int tr_qq = (lane >> 2) & 3, tr_pp = lane & 3, tr_g1 = (lane >> 4) & 1;
 
+    // every key below L_k is staged: [0, L_k)
     auto stage = [&](uint32_t s, int par, int pgv) __attribute__((always_inline)) {
-        paged_dma_step<DP>(p, (const char*)p.kc, kpage_b, khead_b, tst_k, pgv, Lk, s, lds0 + par * STAGE_B, uw, lane);
-        paged_dma_step<DP>(p, (const char*)p.vc, vpage_b, vhead_b, tst_v, pgv, Lk, s, lds0 + 2 * STAGE_B + par * STAGE_B, uw, lane);
+        paged_dma_step<DP>(p, (const char*)p.kc, kpage_b, khead_b, tst_k, pgv, 0u, Lk, s, lds0 + par * STAGE_B, uw, lane);
+        paged_dma_step<DP>(p, (const char*)p.vc, vpage_b, vhead_b, tst_v, pgv, 0u, Lk, s, lds0 + 2 * STAGE_B + par * STAGE_B, uw, lane);
     };
     unsigned vamax = 0;  // bf16: the largest |v| (bits) this thread converted
-    // bf16 -> fp16 (x vmul) in place: the V pieces this wave's own DMA filled (its vmcnt wait is all the ordering needed)
     auto convert = [&](int par, float vmul) __attribute__((always_inline)) {
-        if constexpr (VCONV) {
-#pragma unroll
-            for (int n0 = 0; n0 < NP; n0 += 4) {
-                char* const vq = smem + 2 * STAGE_B + par * STAGE_B + (n0 + uw) * 1024 + lane * 16;
-                const u32x4 x = *(const u32x4*)vq;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned a = x[j] & 0x7fff7fffu, m2 = (a & 0xffffu) > (a >> 16) ? (a & 0xffffu) : (a >> 16);
-                    vamax = vamax > m2 ? vamax : m2;
-                }
-                *(u32x4*)vq = u32x4{bf16x2_to_f16x2_scaled(x[0], vmul), bf16x2_to_f16x2_scaled(x[1], vmul),
-                                    bf16x2_to_f16x2_scaled(x[2], vmul), bf16x2_to_f16x2_scaled(x[3], vmul)};
-            }
-        }
+        if constexpr (VCONV) paged_convert_v<DP>(smem + 2 * STAGE_B + par * STAGE_B, vmul, vamax, uw, lane);
     };
 
     int vexp = 0;
@@ -163,6 +104,9 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
             for (int rr = 0; rr < 16; ++rr) acc[i][rr] = 0.0f;
         float m = -INFINITY, l = 0.0f;  // running max of c S (log2 domain, shared by the halves), this half's sum of P
 
+        // the tile step of fa_paged_device.h (paged_tile), kept in place: as the shared function it cost this kernel alone 1.5 % of its
+        // time on the HBM-bound shapes (profiles/paged_shared/summary.md).  The arithmetic and its order are paged_tile's and must stay
+        // so: a change to either goes into both (test_gpu_varlen_paged.py holds this kernel bitwise to the plain one at equal lengths)
         auto tile_body = [&](const char* Kt, const char* Vt, uint32_t kb, bool v0, bool v1, bool edge) __attribute__((always_inline)) {
             f32x16 s;
             V8 ak[NKS];
@@ -206,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
                     acc[i] = MP::mma(tr_frag<MP, DP>(Vt, i, s2, hi, tr_qq, tr_pp, tr_g1), pb[s2], acc[i]);
         };
 
-        int pg_a = paged_table(p, b, Lk, s0, lane), pg_b = paged_table(p, b, Lk, s0 + 1, lane);  // steps st, st + 1
+        int pg_a = paged_table(p, b, 0u, Lk, s0, lane), pg_b = paged_table(p, b, 0u, Lk, s0 + 1, lane);  // steps st, st + 1
         if (s0 < s1) stage(s0, 0, pg_a);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -214,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
         __syncthreads();
         int par = 0;
         for (uint32_t st = s0; st < s1; ++st) {
-            const int pg_c = paged_table(p, b, Lk, st + 2, lane);  // (its load is waited for with this step's tiles)
+            const int pg_c = paged_table(p, b, 0u, Lk, st + 2, lane);  // (its load is waited for with this step's tiles)
             if (st + 1 < s1) stage(st + 1, par ^ 1, pg_b);  // other buffer: its last readers passed the previous barrier
             if (ks4 || wlive) {
                 const int sub_end = ks4 ? uw + 1 : 4;
@@ -238,48 +182,10 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
         }
         float L = l + xor32(l);
         const bool owner = !ks4 || uw == 0;
-        if (ks4) {
-            // waves 1..3 publish (O^T, m, l) behind the reserved header; wave 0 folds them into its own (every wave passed the loop's
-            // last barrier, so the tile area is free)
-            constexpr int EXW = 16 * NDB + 2;
-            static_assert(FWD16_EPI_RED + 8 <= FWD16_EPI_HDR && (FWD16_EPI_HDR + 3 * EXW * 64) * 4 <= 4 * STAGE_B,
-                          "the exchange lies behind the range rule's words, inside the tile area");
-            float* const ex = (float*)smem + FWD16_EPI_HDR;
-            if (uw > 0) {
-                float* const e = ex + (uw - 1) * EXW * 64 + lane;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) e[(16 * i + rr) * 64] = acc[i][rr];
-                e[(16 * NDB) * 64] = m;
-                e[(16 * NDB + 1) * 64] = L;
-            }
+        if (ks4) {  // the four key quarters meet in the free tile area (fa_paged_device.h)
+            if (uw > 0) paged_ks4_publish<DP, 4 * STAGE_B>(smem, acc, m, L, uw, lane);
             __syncthreads();
-            if (uw == 0) {
-                float mw[3], Mx = m;
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    mw[w] = ex[(w * EXW + 16 * NDB) * 64 + lane];
-                    Mx = fmaxf(Mx, mw[w]);
-                }
-                const float a0 = m == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(m - Mx);
-                L *= a0;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) acc[i][rr] *= a0;
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const float aw = mw[w] == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mw[w] - Mx);
-                    const float* const e = ex + w * EXW * 64 + lane;
-                    L += aw * e[(16 * NDB + 1) * 64];
-#pragma unroll
-                    for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                        for (int rr = 0; rr < 16; ++rr) acc[i][rr] += aw * e[(16 * i + rr) * 64];
-                }
-                m = Mx;
-            }
+            if (uw == 0) paged_ks4_fold<DP>(smem, acc, m, L, lane);
         }
         if constexpr (VCONV) {
             if (pass == 0) {
@@ -334,36 +240,11 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_kernel(PagedVarl
         if (owner && rok) {
             const float f = L > 0.0f ? back / L : 0.0f;
             if constexpr (SPLIT) {
-                const int64_t rows_all = (int64_t)v.Tq * p.H;
-                const int64_t prow = (int64_t)part * rows_all + (int64_t)q0 * p.H + (int64_t)hk * R + r;
-                float* const po = p.part + prow * DP;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int gg = 0; gg < 4; ++gg)
-                        *(f32x4*)(po + 32 * i + 8 * gg + 4 * hi) =
-                            f32x4{acc[i][4 * gg] * f, acc[i][4 * gg + 1] * f, acc[i][4 * gg + 2] * f, acc[i][4 * gg + 3] * f};
-                if (hi == 0) {
-                    typedef float F2 __attribute__((ext_vector_type(2)));
-                    *(F2*)(p.part + (int64_t)p.nsplit * rows_all * DP + prow * 2) = F2{L > 0.0f ? m : -INFINITY, L};
-                }
+                const int64_t rows_all = (int64_t)v.Tq * p.H;  // the packed partial layout (fa_paged_varlen.h)
+                paged_store_part<DP>(p.part, (int64_t)p.nsplit * rows_all, (int64_t)part * rows_all + (int64_t)q0 * p.H + (int64_t)hk * R + r, acc,
+                                     f, m, L, hi);
             } else {
-                const int64_t orow = ((int64_t)(q0 + qi) * p.H + h) * DP;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int gg = 0; gg < 4; ++gg) {
-                        const int64_t at = orow + 32 * i + 8 * gg + 4 * hi;
-                        const f32x4 val = {acc[i][4 * gg] * f, acc[i][4 * gg + 1] * f, acc[i][4 * gg + 2] * f, acc[i][4 * gg + 3] * f};
-                        if constexpr (std::is_same<OUT, float>::value) {
-                            *(f32x4*)((float*)p.out + at) = val;
-                        } else {
-                            typedef OUT O4 __attribute__((ext_vector_type(4)));
-                            *(O4*)((OUT*)p.out + at) = O4{(OUT)val[0], (OUT)val[1], (OUT)val[2], (OUT)val[3]};
-                        }
-                    }
-                if (hi == 0 && p.lse)
-                    p.lse[(int64_t)h * v.Tq + q0 + qi] = L > 0.0f ? (m + __builtin_log2f(L)) * UMFA_LN2 : -INFINITY;
+                paged_store_out<DP, OUT>(p.out, ((int64_t)(q0 + qi) * p.H + h) * DP, p.lse, (int64_t)h * v.Tq + q0 + qi, acc, f, m, L, hi);
             }
         }
         return;

@@ -19,7 +19,7 @@
 
 #include "fa_paged_varlen_fp8.h"
 #include "fa_paged_rope_device.h"
-#include "fa_fwd_16_kernel.h"
+#include "fa_paged_device.h"
 #include "kernels.h"
 
 namespace umfa {
@@ -27,7 +27,7 @@ namespace umfa {
 template <typename T, bool CAUSAL, int DP, typename OUT>
 __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_fp8_kernel(PagedVarlenFp8Params f) {
     BWD16_GEO(DP);
-    (void)TILE_PIECES;
+    (void)TILE_PIECES, (void)PD;
     const PagedVarlenParams& v = f.v;
     const PagedParams& p = v.p;
     constexpr int NS = 2;                    // fp8 stages in the ring
@@ -36,10 +36,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_fp8_kernel(Paged
     constexpr int NP = 128 / (1024 / DP);    // fp8 pieces per step and tensor
     constexpr int PER = 2 * NP / 4;          // LDS-DMA requests per wave and step
     constexpr bool SPLIT = std::is_same<OUT, void>::value;
-    typedef Mma16<T> M;
-    typedef typename M::V8 V8;
-    typedef Mma16<_Float16> MP;  // the P V product: fp16 P, fp16 V
-    typedef typename MP::V8 PV8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ring = smem + 2 * IMG_B;
     const int tid = threadIdx.x, lane = tid & 63, ql = lane & 31, hi = lane >> 5;
@@ -82,17 +78,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_fp8_kernel(Paged
     const uint32_t s0 = part * per, s1 = s0 + per < nst ? s0 + per : nst;
     const float kd = f.kd[(int64_t)b * f.kdb + (int64_t)hk * f.kdh], vd = f.vd[(int64_t)b * f.vdb + (int64_t)hk * f.vdh];
 
-    V8 qf[NKS];
-    const T* qp = (const T*)p.q + (int64_t)(q0 + qi) * p.qst + (int64_t)h * p.qsh;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        if (rok) {
-            qf[ks] = *(const V8*)(qp + 16 * ks + 8 * hi);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[ks][j] = (T)0.0f;
-        }
-    }
+    typename Mma16<T>::V8 qf[NKS];
+    paged_load_q<T, DP>(qf, (const T*)p.q + (int64_t)(q0 + qi) * p.qst + (int64_t)h * p.qsh, rok, hi);
     const float c = p.scale * UMFA_LOG2E * kd;  // scores of the dequantised keys, log2 domain
     const int lim = (int)qi + off;
     const uint32_t tst_k = (uint32_t)p.kst, tst_v = (uint32_t)p.vst;  // fp8: elements are bytes
@@ -119,49 +106,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_fp8_kernel(Paged
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) acc[i][rr] = 0.0f;
     float m = -INFINITY, l = 0.0f;  // running max of c S (log2 domain, shared by the halves), this half's sum of P
-
-    auto tile_body = [&](const char* Kt, const char* Vt, uint32_t kb, bool v0, bool v1, bool edge) __attribute__((always_inline)) {
-        f32x16 s;
-        V8 ak[NKS];
-#pragma unroll
-        for (int ks = 0; ks < PD; ++ks) ak[ks] = *(const V8*)(Kt + d_off<DP>(ql, 2 * ks + hi));
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if (ks + PD < NKS) ak[ks + PD] = *(const V8*)(Kt + d_off<DP>(ql, 2 * (ks + PD) + hi));
-            s = M::mma(ak[ks], qf[ks], ks ? s : f32x16{});
-        }
-        float x[16], mx = -INFINITY;
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const int kr = acc_row(rr, hi);
-            const uint32_t key = kb + kr;
-            x[rr] = s[rr] * c;
-            if (edge && (key >= Lk || !(kr < 16 ? v0 : v1) || (CAUSAL && (int)key > lim))) x[rr] = -INFINITY;
-            mx = fmaxf(mx, x[rr]);
-        }
-        mx = max_xor32(mx);
-        const float mn = fmaxf(m, mx);
-        const float base = mn == -INFINITY ? 0.0f : mn;
-        const float alpha = __builtin_amdgcn_exp2f(m - base);  // (m = -inf: 0)
-        m = mn;
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < NDB; ++i)
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) acc[i][rr] *= alpha;
-        PV8 pb[2];
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const float pr = __builtin_amdgcn_exp2f(x[rr] - base);
-            l += pr;
-            pb[rr >> 3][rr & 7] = (_Float16)pr;
-        }
-#pragma unroll
-        for (int i = 0; i < NDB; ++i)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-                acc[i] = MP::mma(tr_frag<MP, DP>(Vt, i, s2, hi, tr_qq, tr_pp, tr_g1), pb[s2], acc[i]);
-    };
 
     // the block table of super-steps S_cur (tab_c) and S_cur + 1 (tab_n): a step's requests run NS steps ahead of its tiles
     uint32_t S_cur = s0 >> 3;
@@ -203,7 +147,11 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_fp8_kernel(Paged
                 const bool v0 = __builtin_amdgcn_readlane(tab_c, g0) >= 0;
                 const bool v1 = kb + 16 >= Lk || __builtin_amdgcn_readlane(tab_c, g0 + 1) >= 0;
                 const bool edge = kb + 31 >= Lk || !v0 || !v1 || (CAUSAL && (int)kb + 31 > kl_first);
-                tile_body(smem + sub * TILE_BYTES, smem + IMG_B + sub * TILE_BYTES, kb, v0, v1, edge);
+                paged_tile<T, DP>(smem + sub * TILE_BYTES, smem + IMG_B + sub * TILE_BYTES, qf, c, acc, m, l, ql, hi, tr_qq, tr_pp, tr_g1, edge,
+                                  [&](int kr) __attribute__((always_inline)) {
+                                      const uint32_t key = kb + kr;
+                                      return key >= Lk || !(kr < 16 ? v0 : v1) || (CAUSAL && (int)key > lim);
+                                  });
             }
         }
         __syncthreads();
@@ -211,81 +159,19 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_varlen_fp8_kernel(Paged
     }
     float L = l + xor32(l);
     const bool owner = !ks4 || uw == 0;
-    if (ks4) {
-        // waves 1..3 publish (O^T, m, l) behind the reserved header; wave 0 folds them into its own (every wave passed the loop's last
-        // barrier and every request has landed, so the image area is free)
-        constexpr int EXW = 16 * NDB + 2;
-        static_assert((FWD16_EPI_HDR + 3 * EXW * 64) * 4 <= 2 * IMG_B, "the exchange lies inside the image area");
-        float* const ex = (float*)smem + FWD16_EPI_HDR;
-        if (uw > 0) {
-            float* const e = ex + (uw - 1) * EXW * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) e[(16 * i + rr) * 64] = acc[i][rr];
-            e[(16 * NDB) * 64] = m;
-            e[(16 * NDB + 1) * 64] = L;
-        }
+    if (ks4) {  // the four key quarters meet in the free image area (fa_paged_device.h)
+        if (uw > 0) paged_ks4_publish<DP, 2 * IMG_B>(smem, acc, m, L, uw, lane);
         __syncthreads();
-        if (uw == 0) {
-            float mw[3], Mx = m;
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                mw[w] = ex[(w * EXW + 16 * NDB) * 64 + lane];
-                Mx = fmaxf(Mx, mw[w]);
-            }
-            const float a0 = m == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(m - Mx);
-            L *= a0;
-#pragma unroll
-            for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) acc[i][rr] *= a0;
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                const float aw = mw[w] == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mw[w] - Mx);
-                const float* const e = ex + w * EXW * 64 + lane;
-                L += aw * e[(16 * NDB + 1) * 64];
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) acc[i][rr] += aw * e[(16 * i + rr) * 64];
-            }
-            m = Mx;
-        }
+        if (uw == 0) paged_ks4_fold<DP>(smem, acc, m, L, lane);
     }
     if (owner && rok) {
         const float fo = L > 0.0f ? vd / L : 0.0f;  // v_descale: fp32, behind the product
         if constexpr (SPLIT) {
             const int64_t rows_all = (int64_t)v.Tq * p.H;  // the packed partial layout (fa_paged_varlen.h)
-            const int64_t prow = (int64_t)part * rows_all + (int64_t)q0 * p.H + (int64_t)hk * R + r;
-            float* const po = p.part + prow * DP;
-#pragma unroll
-            for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg)
-                    *(f32x4*)(po + 32 * i + 8 * gg + 4 * hi) =
-                        f32x4{acc[i][4 * gg] * fo, acc[i][4 * gg + 1] * fo, acc[i][4 * gg + 2] * fo, acc[i][4 * gg + 3] * fo};
-            if (hi == 0) {
-                typedef float F2 __attribute__((ext_vector_type(2)));
-                *(F2*)(p.part + (int64_t)p.nsplit * rows_all * DP + prow * 2) = F2{L > 0.0f ? m : -INFINITY, L};
-            }
+            paged_store_part<DP>(p.part, (int64_t)p.nsplit * rows_all, (int64_t)part * rows_all + (int64_t)q0 * p.H + (int64_t)hk * R + r, acc, fo,
+                                 m, L, hi);
         } else {
-            const int64_t orow = ((int64_t)(q0 + qi) * p.H + h) * DP;
-#pragma unroll
-            for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    const int64_t at = orow + 32 * i + 8 * gg + 4 * hi;
-                    const f32x4 val = {acc[i][4 * gg] * fo, acc[i][4 * gg + 1] * fo, acc[i][4 * gg + 2] * fo, acc[i][4 * gg + 3] * fo};
-                    if constexpr (std::is_same<OUT, float>::value) {
-                        *(f32x4*)((float*)p.out + at) = val;
-                    } else {
-                        typedef OUT O4 __attribute__((ext_vector_type(4)));
-                        *(O4*)((OUT*)p.out + at) = O4{(OUT)val[0], (OUT)val[1], (OUT)val[2], (OUT)val[3]};
-                    }
-                }
-            if (hi == 0 && p.lse)
-                p.lse[(int64_t)h * v.Tq + q0 + qi] = L > 0.0f ? (m + __builtin_log2f(L)) * UMFA_LN2 : -INFINITY;
+            paged_store_out<DP, OUT>(p.out, ((int64_t)(q0 + qi) * p.H + h) * DP, p.lse, (int64_t)h * v.Tq + q0 + qi, acc, fo, m, L, hi);
         }
     }
 }

@@ -1,9 +1,9 @@
 // fa_fwd_16_paged_window.hip -- bf16 / fp16 MFMA forward over a paged or static KV cache with a sliding window (flash-attention's
 // window_size), head_dim 64 / 128, GQA.  Semantics: fa_paged_window.h; layout and memory safety: fa_paged.h.
 //
-// fa_fwd16_paged_kernel (fa_fwd_16_paged.hip: its row packing, its 128-key steps of four 32-key subtiles, its page indirection, its bf16
-// V conversion with the range rule, its decode form and its split-KV parts) with the banded sweep of fa_fwd_16_varlen_window.hip: row i
-// sees keys [i + off - left, i + off + right], off = L_k - Sq, the bounds runtime values (no causal instantiation).
+// fa_fwd16_paged_kernel's shell (fa_fwd_16_paged.hip: its row packing, its 128-key steps, its decode form and its split-KV parts) over
+// the shared device pieces of fa_paged_device.h, with the banded sweep of fa_fwd_16_varlen_window.hip: row i sees keys [i + off - left,
+// i + off + right], off = L_k - Sq, the bounds runtime values (no causal instantiation).
 //
 // Step range: with first_tok / last_tok the query tokens of the workgroup's first and last live rows, k_first = max(0, first_tok + off -
 // left) and k_last = min(L_k - 1, last_tok + off + right); the workgroup visits the steps [k_first / 128, k_last / 128 + 1), none when
@@ -21,63 +21,18 @@
 #include <type_traits>
 
 #include "fa_paged_window.h"
-#include "fa_fwd_16_kernel.h"
+#include "fa_paged_device.h"
 #include "kernels.h"
 
 namespace umfa {
 
-namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// lanes 0 .. 7 (and again 8 .. 15, ...): the physical page of 16-key group (lane & 7) of step s (keys 128 s .. 128 s + 127), -1 for an
-// entry outside the pool or a group wholly outside the workgroup's keys [kfirst, Le) (its entry is not read).  One vector load per step,
-// issued a step ahead of its use (fa_fwd_16_paged.hip paged_table).
-__device__ __forceinline__ int paged_table(const PagedParams& p, uint32_t b, uint32_t kfirst, uint32_t Le, uint32_t s, int lane) {
-    const uint32_t key = s * 128 + 16 * (uint32_t)(lane & 7);
-    return key < Le && key + 15 >= kfirst ? paged_page(p, b, paged_lpage(p, key)) : -1;
-}
-
-// LDS-DMA of step s of one cache tensor, KV head at head_b bytes, into the 128-row swizzled image at lds_dst (pgv: paged_table of step
-// s): piece n (RPP rows) goes to lds_dst + n KiB, wave uw issues pieces uw, uw + 4, ...  Rows of keys at or past Le lie past the
-// descriptor's range, rows of keys below kfirst are sent there: both land as zeros.
-template <int DP>
-__device__ __forceinline__ void paged_dma_step(const PagedParams& p, const char* pool, int64_t page_b, int64_t head_b, uint32_t tst_b,
-                                               int pgv, uint32_t kfirst, uint32_t Le, uint32_t s, unsigned lds_dst, int uw, int lane) {
-    constexpr int ROW_B = 2 * DP, NCH = DP / 8, RPP = 1024 / ROW_B, NP = 128 / RPP;
-    const int r = lane / NCH, c = lane % NCH;
-#pragma nounroll
-    for (int n0 = 0; n0 < NP; n0 += 4) {  // (one piece at a time: unrolled, the descriptors of all pieces ran out of scalar registers)
-        const int n = n0 + uw;
-        const uint32_t key0 = s * 128 + (uint32_t)(RPP * n);
-        const uint32_t lp = paged_lpage(p, key0);
-        const int pg = __builtin_amdgcn_readlane(pgv, (RPP * n) / 16);  // (the step's page of this piece's 16-key group: paged_table)
-        const uint32_t pstart = lp * p.page_size;
-        uint32_t nv = Le > pstart ? Le - pstart : 0u;
-        nv = nv < p.page_size ? nv : p.page_size;
-        const uint32_t bytes = pg >= 0 && nv ? (nv - 1) * tst_b + ROW_B : 0u;
-        const i32x4 srd = make_srd(pool + (int64_t)(pg >= 0 ? pg : 0) * page_b + head_b, bytes);
-        const int row = RPP * n + r;
-        const int voff = key0 + (uint32_t)r < kfirst ? (int)bytes
-                                                     : (int)((key0 - pstart + (uint32_t)r) * tst_b) + (d_off<DP>(row, c) - row * ROW_B);
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                     ::"s"(lds_dst + n * 1024), "v"(voff), "s"(srd) : "memory");
-    }
-}
-
-}  // namespace
-
 template <typename T, int DP, typename OUT>
 __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWindowParams pw) {
     BWD16_GEO(DP);
+    (void)TILE_PIECES, (void)PD;
     constexpr int STAGE_B = 4 * TILE_BYTES;  // one step (128 keys) of K or of V
-    constexpr int NP = 128 / (1024 / ROW_B);  // pieces per step and tensor
     constexpr bool VCONV = std::is_same<T, __bf16>::value;
     constexpr bool SPLIT = std::is_same<OUT, void>::value;
-    typedef Mma16<T> M;
-    typedef typename M::V8 V8;
-    typedef Mma16<_Float16> MP;  // the P V product: fp16 P, fp16 V
-    typedef typename MP::V8 PV8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PagedParams& p = pw.p;
     const int tid = threadIdx.x, lane = tid & 63, ql = lane & 31, hi = lane >> 5;
@@ -110,17 +65,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWind
     const uint32_t per = (ws_hi - ws_lo + p.nsplit - 1) / p.nsplit;  // the parts divide the band's steps
     const uint32_t s0r = ws_lo + part * per, s0 = s0r < ws_hi ? s0r : ws_hi, s1 = s0 + per < ws_hi ? s0 + per : ws_hi;
 
-    V8 qf[NKS];
-    const T* qp = (const T*)p.q + (int64_t)b * p.qsb + (int64_t)qi * p.qst + (int64_t)h * p.qsh;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-        if (rok) {
-            qf[ks] = *(const V8*)(qp + 16 * ks + 8 * hi);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[ks][j] = (T)0.0f;
-        }
-    }
+    typename Mma16<T>::V8 qf[NKS];
+    paged_load_q<T, DP>(qf, (const T*)p.q + (int64_t)b * p.qsb + (int64_t)qi * p.qst + (int64_t)h * p.qsh, rok, hi);
     const float c = p.scale * UMFA_LOG2E;
     const int lim_lo = (int)qi + lo_off, lim_hi = (int)qi + hi_off;
     const uint32_t tst_k = (uint32_t)p.kst * 2, tst_v = (uint32_t)p.vst * 2;
@@ -133,22 +79,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWind
         paged_dma_step<DP>(p, (const char*)p.vc, vpage_b, vhead_b, tst_v, pgv, kfirst, Le, s, lds0 + 2 * STAGE_B + par * STAGE_B, uw, lane);
     };
     unsigned vamax = 0;  // bf16: the largest |v| (bits) this thread converted
-    // bf16 -> fp16 (x vmul) in place: the V pieces this wave's own DMA filled (its vmcnt wait is all the ordering needed)
     auto convert = [&](int par, float vmul) __attribute__((always_inline)) {
-        if constexpr (VCONV) {
-#pragma unroll
-            for (int n0 = 0; n0 < NP; n0 += 4) {
-                char* const vq = smem + 2 * STAGE_B + par * STAGE_B + (n0 + uw) * 1024 + lane * 16;
-                const u32x4 x = *(const u32x4*)vq;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned a = x[j] & 0x7fff7fffu, m2 = (a & 0xffffu) > (a >> 16) ? (a & 0xffffu) : (a >> 16);
-                    vamax = vamax > m2 ? vamax : m2;
-                }
-                *(u32x4*)vq = u32x4{bf16x2_to_f16x2_scaled(x[0], vmul), bf16x2_to_f16x2_scaled(x[1], vmul),
-                                    bf16x2_to_f16x2_scaled(x[2], vmul), bf16x2_to_f16x2_scaled(x[3], vmul)};
-            }
-        }
+        if constexpr (VCONV) paged_convert_v<DP>(smem + 2 * STAGE_B + par * STAGE_B, vmul, vamax, uw, lane);
     };
 
     int vexp = 0;
@@ -160,49 +92,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWind
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) acc[i][rr] = 0.0f;
         float m = -INFINITY, l = 0.0f;  // running max of c S (log2 domain, shared by the halves), this half's sum of P
-
-        auto tile_body = [&](const char* Kt, const char* Vt, uint32_t kb, bool v0, bool v1, bool edge) __attribute__((always_inline)) {
-            f32x16 s;
-            V8 ak[NKS];
-#pragma unroll
-            for (int ks = 0; ks < PD; ++ks) ak[ks] = *(const V8*)(Kt + d_off<DP>(ql, 2 * ks + hi));
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                if (ks + PD < NKS) ak[ks + PD] = *(const V8*)(Kt + d_off<DP>(ql, 2 * (ks + PD) + hi));
-                s = M::mma(ak[ks], qf[ks], ks ? s : f32x16{});
-            }
-            float x[16], mx = -INFINITY;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int kr = acc_row(rr, hi);
-                const int key = (int)kb + kr;
-                x[rr] = s[rr] * c;
-                if (edge && (key >= (int)Lk || !(kr < 16 ? v0 : v1) || key < lim_lo || key > lim_hi)) x[rr] = -INFINITY;
-                mx = fmaxf(mx, x[rr]);
-            }
-            mx = max_xor32(mx);
-            const float mn = fmaxf(m, mx);
-            const float base = mn == -INFINITY ? 0.0f : mn;
-            const float alpha = __builtin_amdgcn_exp2f(m - base);  // (m = -inf: 0)
-            m = mn;
-            l *= alpha;
-#pragma unroll
-            for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) acc[i][rr] *= alpha;
-            PV8 pb[2];
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const float pr = __builtin_amdgcn_exp2f(x[rr] - base);
-                l += pr;
-                pb[rr >> 3][rr & 7] = (_Float16)pr;
-            }
-#pragma unroll
-            for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-                    acc[i] = MP::mma(tr_frag<MP, DP>(Vt, i, s2, hi, tr_qq, tr_pp, tr_g1), pb[s2], acc[i]);
-        };
 
         int pg_a = paged_table(p, b, kfirst, Le, s0, lane), pg_b = paged_table(p, b, kfirst, Le, s0 + 1, lane);  // steps st, st + 1
         if (s0 < s1) stage(s0, 0, pg_a);
@@ -224,7 +113,11 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWind
                     const bool v0 = __builtin_amdgcn_readlane(pg_a, 2 * sub) >= 0;
                     const bool v1 = kb + 16 >= Le || __builtin_amdgcn_readlane(pg_a, 2 * sub + 1) >= 0;
                     const bool edge = kb + 31 >= Lk || !v0 || !v1 || (int)kb < wlo_last || (int)kb + 31 > whi_first;
-                    tile_body(smem + par * STAGE_B + sub * TILE_BYTES, smem + 2 * STAGE_B + par * STAGE_B + sub * TILE_BYTES, kb, v0, v1, edge);
+                    paged_tile<T, DP>(smem + par * STAGE_B + sub * TILE_BYTES, smem + 2 * STAGE_B + par * STAGE_B + sub * TILE_BYTES, qf, c, acc, m,
+                                      l, ql, hi, tr_qq, tr_pp, tr_g1, edge, [&](int kr) __attribute__((always_inline)) {
+                                          const int key = (int)kb + kr;
+                                          return key >= (int)Lk || !(kr < 16 ? v0 : v1) || key < lim_lo || key > lim_hi;
+                                      });
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -237,46 +130,10 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWind
         }
         float L = l + xor32(l);
         const bool owner = !ks4 || uw == 0;
-        if (ks4) {
-            // waves 1..3 publish (O^T, m, l) behind the reserved header; wave 0 folds them into its own (every wave passed the loop's
-            // last barrier, so the tile area is free)
-            constexpr int EXW = 16 * NDB + 2;
-            float* const ex = (float*)smem + FWD16_EPI_HDR;
-            if (uw > 0) {
-                float* const e = ex + (uw - 1) * EXW * 64 + lane;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) e[(16 * i + rr) * 64] = acc[i][rr];
-                e[(16 * NDB) * 64] = m;
-                e[(16 * NDB + 1) * 64] = L;
-            }
+        if (ks4) {  // the four key quarters meet in the free tile area (fa_paged_device.h)
+            if (uw > 0) paged_ks4_publish<DP, 4 * STAGE_B>(smem, acc, m, L, uw, lane);
             __syncthreads();
-            if (uw == 0) {
-                float mw[3], Mx = m;
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    mw[w] = ex[(w * EXW + 16 * NDB) * 64 + lane];
-                    Mx = fmaxf(Mx, mw[w]);
-                }
-                const float a0 = m == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(m - Mx);
-                L *= a0;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) acc[i][rr] *= a0;
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const float aw = mw[w] == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mw[w] - Mx);
-                    const float* const e = ex + w * EXW * 64 + lane;
-                    L += aw * e[(16 * NDB + 1) * 64];
-#pragma unroll
-                    for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                        for (int rr = 0; rr < 16; ++rr) acc[i][rr] += aw * e[(16 * i + rr) * 64];
-                }
-                m = Mx;
-            }
+            if (uw == 0) paged_ks4_fold<DP>(smem, acc, m, L, lane);
         }
         if constexpr (VCONV) {
             if (pass == 0) {
@@ -332,35 +189,10 @@ __global__ __launch_bounds__(256, 2) void fa_fwd16_paged_window_kernel(PagedWind
             const float f = L > 0.0f ? back / L : 0.0f;
             if constexpr (SPLIT) {
                 const int64_t rows_all = (int64_t)p.B * p.Hkv * p.R;
-                const int64_t prow = (int64_t)part * rows_all + (int64_t)bk * p.R + r;
-                float* const po = p.part + prow * DP;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int gg = 0; gg < 4; ++gg)
-                        *(f32x4*)(po + 32 * i + 8 * gg + 4 * hi) =
-                            f32x4{acc[i][4 * gg] * f, acc[i][4 * gg + 1] * f, acc[i][4 * gg + 2] * f, acc[i][4 * gg + 3] * f};
-                if (hi == 0) {
-                    typedef float F2 __attribute__((ext_vector_type(2)));
-                    *(F2*)(p.part + (int64_t)p.nsplit * rows_all * DP + prow * 2) = F2{L > 0.0f ? m : -INFINITY, L};
-                }
+                paged_store_part<DP>(p.part, (int64_t)p.nsplit * rows_all, (int64_t)part * rows_all + (int64_t)bk * p.R + r, acc, f, m, L, hi);
             } else {
-                const int64_t orow = (((int64_t)b * p.Sq + qi) * p.H + h) * DP;
-#pragma unroll
-                for (int i = 0; i < NDB; ++i)
-#pragma unroll
-                    for (int gg = 0; gg < 4; ++gg) {
-                        const int64_t at = orow + 32 * i + 8 * gg + 4 * hi;
-                        const f32x4 val = {acc[i][4 * gg] * f, acc[i][4 * gg + 1] * f, acc[i][4 * gg + 2] * f, acc[i][4 * gg + 3] * f};
-                        if constexpr (std::is_same<OUT, float>::value) {
-                            *(f32x4*)((float*)p.out + at) = val;
-                        } else {
-                            typedef OUT O4 __attribute__((ext_vector_type(4)));
-                            *(O4*)((OUT*)p.out + at) = O4{(OUT)val[0], (OUT)val[1], (OUT)val[2], (OUT)val[3]};
-                        }
-                    }
-                if (hi == 0 && p.lse)
-                    p.lse[((int64_t)b * p.H + h) * p.Sq + qi] = L > 0.0f ? (m + __builtin_log2f(L)) * UMFA_LN2 : -INFINITY;
+                paged_store_out<DP, OUT>(p.out, (((int64_t)b * p.Sq + qi) * p.H + h) * DP, p.lse, ((int64_t)b * p.H + h) * p.Sq + qi, acc, f, m,
+                                         L, hi);
             }
         }
         return;
@@ -398,9 +230,7 @@ static hipError_t launch_fwd16_paged_window_d(const PagedWindowParams& w, hipStr
 // w.p.nsplit > 1: w.p.part holds nsplit B H_kv R (D + 2) floats
 hipError_t launch_fwd_16_paged_window(const PagedWindowParams& w, hipStream_t stream, const char** name) {
     const PagedParams& p = w.p;
-    if (!paged_window_supported(w) || !p.out || ((uintptr_t)p.out & 15) || ((uintptr_t)p.lse & 3) || p.nsplit == 0) return hipErrorInvalidValue;
-    if (p.out_prec != P_FP32 && p.out_prec != p.in_prec) return hipErrorInvalidValue;
-    if (p.R != (p.H / p.Hkv) * p.Sq || p.nrb != (p.ks4 ? 1u : (p.R + 127) / 128) || (p.ks4 && p.R > 32)) return hipErrorInvalidValue;
+    if (!paged_window_supported(w) || !paged_fwd_args_ok(p)) return hipErrorInvalidValue;
     static const char* const names[2][2][2] = {
         {{"fa_fwd16_paged_window<fp16,64>", "fa_fwd16_paged_window<fp16,64,split>"},
          {"fa_fwd16_paged_window<fp16,128>", "fa_fwd16_paged_window<fp16,128,split>"}},

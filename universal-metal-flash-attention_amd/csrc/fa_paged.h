@@ -45,6 +45,7 @@ bool paged_supported(const PagedParams& p);
 hipError_t launch_paged_append(const PagedParams& p, hipStream_t stream);
 hipError_t launch_fwd_16_paged(const PagedParams& p, hipStream_t stream, const char** name);
 hipError_t launch_paged_fold(const PagedParams& p, hipStream_t stream);  // the split-KV fold alone (p.nsplit parts in p.part)
+bool paged_fwd_args_ok(const PagedParams& p);  // out / lse alignment, out_prec and R / nrb / ks4: the checks the forward launchers share
 
 namespace {
 
