@@ -712,6 +712,38 @@ mfa_error_t umfa_kvcache_attention_window_forward_stream(mfa_context_t context, 
                                                          uint32_t rotary_dim, bool rotary_interleaved, int32_t window_left,
                                                          int32_t window_right);
 
+/* MI355X extra: sliding-window attention for packed variable-length queries over a 16-bit paged or static KV cache
+ * (flash_attn_varlen_func(..., block_table=, window_size=)): the call a continuous-batching server makes for layers that attend to a
+ * local window.  The arguments are umfa_varlen_kvcache_attention_rope_forward_stream's followed by the window; rotary_cos == rotary_sin
+ * == NULL means no rotary (the other rotary arguments are then ignored), exactly one of them NULL is MFA_ERROR_INVALID_ARGS.  There are
+ * no fp8 arguments: fp8 caches with a window are not built.
+ *   The contract is umfa_varlen_kvcache_attention_forward_stream's with umfa_kvcache_attention_window_forward_stream's bound applied per
+ *   sequence.  For sequence b, L_q,b = cu[b+1] - cu[b] (cu values clamped into [0, total_q], L_q,b to max_seqlen_q), L0_b =
+ *   clamp(cache_seqlens[b], 0, cap), L_k,b = min(L0_b + L_q,b, cap) with has_new and L0_b without, and off_b = L_k,b - L_q,b.  Query
+ *   token i of sequence b sees key j iff j < L_k,b, j's page entry lies in [0, num_pages) and i + off_b - window_left <= j <= i + off_b +
+ *   window_right.  A side given as -1 is unbounded; a value below -1 is MFA_ERROR_INVALID_ARGS.  causal sets window_right = 0 (and, with
+ *   rotary, places the query positions as in the rotary entry: the window does not).  A row that sees no key gives O = 0 exactly and
+ *   LSE = -inf.  Rows no sequence covers are not written.  The append, the clamps, the dropped rows, memory safety for any contents of
+ *   cu_seqlens_q, cache_seqlens and the block table, and the fused rotary pre-pass are the packed and rotary entries', word for word.
+ *   window_left >= capacity (max_pages_per_seq * page_size; static: page_size) and window_right >= max_seqlen_q cannot bind and count
+ *   as unbounded.  A window with both sides unbounded -- or the left unbounded, the right 0 and causal set -- launches the unwindowed
+ *   kernels of the packed / rotary entry, bit for bit; every other window takes the banded kernel: each work item sweeps only the
+ *   128-key steps its own rows' band touches, and split-KV parts (one count per launch) divide those steps, so the cost follows the band
+ *   and not the context.  num_splits 0 chooses the part count from the item bound and the band's length; with every L_q,b equal that is
+ *   umfa_kvcache_attention_window_forward_stream's choice, and the result equals that entry's bit for bit at the same num_splits.
+ *   Block-table entries of 16-key groups wholly outside an item's band are never read.  The capacity and max_seqlen_q must be below
+ *   2^30 (MFA_ERROR_INVALID_ARGS otherwise).  Stream capture (after a warm-up call), the pooled workspace and the error codes are the
+ *   packed entry's; umfa_varlen_kvcache_item_counts reads this call's tally too.  In-stream, never synchronising. */
+mfa_error_t umfa_varlen_kvcache_attention_window_forward_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache, const int64_t* k_cache_strides,
+    void* v_cache, const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides, const void* v_new,
+    const int64_t* v_new_strides, const int32_t* block_table, int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+    uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads, uint32_t num_kv_heads,
+    uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+    int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const void* rotary_cos,
+    const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
+    bool rotary_interleaved, int32_t window_left, int32_t window_right);
+
 /* MI355X extra: umfa_attention_backward_stream for grouped-query attention without expanded K / V copies (the reference
  * expands them with repeat_interleave before both passes, metal_sdpa_backend.cpp:1694-1702).  k, v, dk, dv:
  * [B, num_kv_heads, Skv, D]; everything else as umfa_attention_backward_stream.  16-bit MFMA backward only (16-bit

@@ -1,7 +1,8 @@
 // runtime_paged_varlen.hip -- the C ABI of packed variable-length queries over a paged / static KV cache (include/umfa_abi.h):
 // umfa_varlen_kvcache_attention_forward_stream, with the rotary embedding of q and k_new fused into the append launch
 // (fa_paged_rope.h) umfa_varlen_kvcache_attention_rope_forward_stream, and over an fp8 (e4m3fn) cache with per-(sequence, KV head)
-// descales, with or without rotary (fa_paged_varlen_fp8.h), umfa_varlen_kvcache_attention_fp8_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
+// descales, with or without rotary (fa_paged_varlen_fp8.h), umfa_varlen_kvcache_attention_fp8_forward_stream, and with a sliding window
+// over a 16-bit cache (fa_paged_varlen_window.h) umfa_varlen_kvcache_attention_window_forward_stream.  In-stream, never synchronising: cu_seqlens_q, cache_seqlens and the block table stay on
 // the device, so a captured graph follows their contents on replay.  Launch order on the stream: the packed append of k_new / v_new
 // (when given), the item-list pre-pass, the attention, and with split-KV the fold.  The item list and the split partials come from the
 // stream's pooled workspace (a capture that would have to grow it returns MFA_ERROR_MEMORY_ALLOCATION: warm up first).  Anything
@@ -12,6 +13,7 @@
 #include "fa_paged_varlen.h"
 #include "fa_paged_rope.h"
 #include "fa_paged_varlen_fp8.h"
+#include "fa_paged_varlen_window.h"
 
 using namespace umfa;
 using namespace umfa_rt;
@@ -46,6 +48,27 @@ uint32_t pv_auto_splits(const PagedVarlenParams& v, int ncu) {
     return (uint32_t)(n < 64 ? n : 64);
 }
 
+// the band of a window call, normalised by the entry: each side a bound that binds or PAGED_WIN_OPEN
+struct PvWindowArgs {
+    int left, right;
+};
+
+// pv_auto_splits' rule with the length capped by the band instead of the capacity, as kvcache_window_attention caps it
+// (runtime_paged.hip paged_window_auto_splits): an item visits the steps of at most left + right + max_seqlen_q keys (an open side: the
+// capacity), plus one step for a band that straddles a step boundary.  With every L_q equal both entries choose the same.
+uint32_t pv_window_auto_splits(const PagedVarlenParams& v, const PvWindowArgs& w, int ncu) {
+    const uint64_t items = v.n_items;
+    const uint64_t slots = (uint64_t)ncu * (v.p.D == 128 ? 1 : 2);
+    if (items == 0 || items >= slots) return 1;
+    uint64_t n = (slots + items - 1) / items;
+    const uint64_t cap = (uint64_t)v.p.max_pages * v.p.page_size;
+    const uint64_t band = (w.left == PAGED_WIN_OPEN ? cap : (uint64_t)w.left) + (w.right == PAGED_WIN_OPEN ? cap : (uint64_t)w.right) + v.p.Sq;
+    const uint64_t steps = ((band < cap ? band : cap) + 127) / 128 + 1;
+    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
+    n = n < by_len ? n : by_len;
+    return (uint32_t)(n < 64 ? n : 64);
+}
+
 constexpr size_t PV_HDR_B = 256;  // the tally's words at the front of the workspace block
 
 }  // namespace
@@ -53,7 +76,9 @@ constexpr size_t PV_HDR_B = 256;  // the tally's words at the front of the works
 namespace {
 
 // every entry; rope != NULL: the fused pre-pass (fa_paged_rope.h) stands in for the packed append and the attention reads its q image;
-// f8 != NULL: the cache is e4m3fn with f8's descales (cache strides in bytes) and the kernels are fa_fwd_16_paged_varlen_fp8.hip's
+// f8 != NULL: the cache is e4m3fn with f8's descales (cache strides in bytes) and the kernels are fa_fwd_16_paged_varlen_fp8.hip's;
+// win != NULL (16-bit caches): the banded kernel (fa_paged_varlen_window.h) stands in for the attention, `causal` then only places the
+// rotary positions of q
 mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache,
                                    const int64_t* k_cache_strides, void* v_cache, const int64_t* v_cache_strides, const void* k_new,
                                    const int64_t* k_new_strides, const void* v_new, const int64_t* v_new_strides, const int32_t* block_table,
@@ -62,8 +87,9 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
                                    uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
                                    uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision, void* out,
                                    int32_t out_precision, float* lse, int32_t num_splits, const RopeArgs* rope,
-                                   const PagedVarlenFp8Params* f8 = nullptr) {
+                                   const PagedVarlenFp8Params* f8 = nullptr, const PvWindowArgs* win = nullptr) {
     Context* ctx = as_ctx(context);
+    if (win && f8) return MFA_ERROR_INVALID_ARGS;
     if (rope && (!has_new || !rope->cos || !rope->sin || rope->table_f32 < 0))
         return MFA_ERROR_INVALID_ARGS;
     if (!ctx || !out || !q || !k_cache || !v_cache || !cache_seqlens || !cu_seqlens_q || !k_cache_strides || !v_cache_strides)
@@ -107,13 +133,17 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
     if (num_kv_heads == 0 || num_heads % num_kv_heads) return MFA_ERROR_INVALID_ARGS;
     p.nsplit = 1;
     v.n_items = paged_varlen_item_bound(v);
-    auto supported = [&]() { return f8 ? paged_varlen_fp8_supported(f) : paged_varlen_supported(v); };
+    auto supported = [&]() {
+        return f8 ? paged_varlen_fp8_supported(f) : win ? paged_varlen_window_supported(PagedVarlenWindowParams{v, win->left, win->right}) : paged_varlen_supported(v);
+    };
     if (!supported() || ((uintptr_t)out & 15) || ((uintptr_t)lse & 3)) return MFA_ERROR_INVALID_ARGS;
     const char* name = "none";
     std::lock_guard<std::mutex> lock(ctx->mu);
     const int dev = stream_device((hipStream_t)stream);
     DeviceGuard guard(dev);
-    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : pv_auto_splits(v, pv_cu_count(dev));
+    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256)
+               : win          ? pv_window_auto_splits(v, *win, pv_cu_count(dev))
+                              : pv_auto_splits(v, pv_cu_count(dev));
     if (!supported()) return MFA_ERROR_INVALID_ARGS;
     PagedRopeParams r;
     memset(&r, 0, sizeof(r));
@@ -156,7 +186,10 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
         const hipError_t e = f8 ? launch_paged_varlen_fp8_append(f, (hipStream_t)stream) : launch_paged_varlen_append(v, (hipStream_t)stream);
         if (e != hipSuccess) return rc_pv(e);
     }
-    const hipError_t e = f8 ? launch_fwd_16_paged_varlen_fp8(f, (hipStream_t)stream, &name) : launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
+    // (v as it stands here: the rotary path has pointed p.q at its image by now)
+    const hipError_t e = f8    ? launch_fwd_16_paged_varlen_fp8(f, (hipStream_t)stream, &name)
+                         : win ? launch_fwd_16_paged_varlen_window(PagedVarlenWindowParams{v, win->left, win->right}, (hipStream_t)stream, &name)
+                               : launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
     ctx->last_kernel = name;
     return rc_pv(e);
 }
@@ -219,6 +252,35 @@ mfa_error_t umfa_varlen_kvcache_attention_fp8_forward_stream(
                                   cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
                                   softmax_scale, causal, input_precision, out, out_precision, lse, num_splits, rotary_cos ? &rope : nullptr,
                                   &f8);
+}
+
+mfa_error_t umfa_varlen_kvcache_attention_window_forward_stream(
+    mfa_context_t context, void* stream, const void* q, const int64_t* q_strides, void* k_cache, const int64_t* k_cache_strides,
+    void* v_cache, const int64_t* v_cache_strides, const void* k_new, const int64_t* k_new_strides, const void* v_new,
+    const int64_t* v_new_strides, const int32_t* block_table, int64_t block_table_stride, const int32_t* cache_seqlens, uint32_t total_q,
+    uint32_t batch, uint32_t max_seqlen_q, const int32_t* cu_seqlens_q, bool has_new, uint32_t num_heads, uint32_t num_kv_heads,
+    uint16_t head_dim, uint32_t page_size, uint32_t num_pages, uint32_t max_pages_per_seq, float softmax_scale, bool causal,
+    int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const void* rotary_cos,
+    const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
+    bool rotary_interleaved, int32_t window_left, int32_t window_right) {
+    if (window_left < -1 || window_right < -1) return MFA_ERROR_INVALID_ARGS;
+    if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
+    // the window, normalised once: causal is right = 0; a side that cannot bind (left >= capacity, right >= max_seqlen_q) is open
+    const uint64_t cap = block_table ? (uint64_t)max_pages_per_seq * page_size : (uint64_t)page_size;
+    if (cap >= (1ull << 30) || max_seqlen_q >= (1u << 30)) return MFA_ERROR_INVALID_ARGS;
+    if (causal) window_right = 0;
+    PvWindowArgs w;
+    w.left = window_left < 0 || (uint64_t)window_left >= cap ? PAGED_WIN_OPEN : window_left;
+    w.right = window_right < 0 || (uint32_t)window_right >= max_seqlen_q ? PAGED_WIN_OPEN : window_right;
+    // a window that bounds nothing (or only as causal does): the unwindowed packed kernels, unchanged
+    const bool plain = w.left == PAGED_WIN_OPEN && (w.right == PAGED_WIN_OPEN || (causal && w.right == 0));
+    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
+    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
+                                  v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
+                                  cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
+                                  softmax_scale, causal, input_precision, out, out_precision, lse, num_splits, rotary_cos ? &rope : nullptr,
+                                  nullptr, plain ? nullptr : &w);
 }
 
 // debug: the tally of the last umfa_varlen_kvcache_attention_forward_stream call on `stream` (nothing else may have used the stream's

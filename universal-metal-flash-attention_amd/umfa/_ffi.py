@@ -220,6 +220,10 @@ def _load_library(path: str | None = None) -> ctypes.CDLL:
                 [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,
                  _u32, _u32, _u32, _u32, _u32, _u16, _u32, _u32, _u32, _f32, _b, _i32, _vp, _i32, _vp, _i32, _b, _vp, _i64p, _vp, _i64p]
                 + _ROPE + [_i32, _i32])
+        if path is None or hasattr(lib, "umfa_varlen_kvcache_attention_window_forward_stream"):  # packed queries with a sliding window (include/umfa_abi.h)
+            sig("umfa_varlen_kvcache_attention_window_forward_stream", mfa_error_t,
+                [mfa_context_t, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, ctypes.c_int64, _vp,
+                 _u32, _u32, _u32, _vp, _b, _u32, _u32, _u16, _u32, _u32, _u32, _f32, _b, _i32, _vp, _i32, _vp, _i32] + _ROPE + [_i32, _i32])
     if path is None or hasattr(lib, "umfa_release_scratch"):
         sig("umfa_release_scratch", mfa_error_t, [mfa_context_t, _vp, _i32])
     if path is None or hasattr(lib, "umfa_set_option"):  # (tools/ab_inproc.py also loads older builds by explicit path)

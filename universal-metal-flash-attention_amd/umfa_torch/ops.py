@@ -802,6 +802,31 @@ def varlen_kvcache_attention_fp8_forward(q, k_cache, v_cache, cu_seqlens_q, max_
                                    max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype, out, lse)
 
 
+def varlen_kvcache_attention_window_forward(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, block_table=None, k_new=None,
+                                            v_new=None, *, scale: float, causal: bool = False, window=(-1, -1), num_splits: int = 0,
+                                            rotary_cos=None, rotary_sin=None, rotary_interleaved: bool = False, out_dtype=None, out=None,
+                                            lse=None):
+    """varlen_kvcache_attention_forward with a sliding window (umfa_varlen_kvcache_attention_window_forward_stream): window = (left,
+    right), flash-attention's window_size -- with off_b = L_k,b - L_q,b, query token i of sequence b sees keys i + off_b - left ..
+    i + off_b + right of the L_k,b the packed call covers; -1 is unbounded, causal sets right = 0.  16-bit caches.  With rotary_cos /
+    rotary_sin the rotary embedding is fused into the packed append launch as in varlen_kvcache_attention_rope_forward (new tokens
+    required).  The entry normalises the window; one that bounds nothing runs the unwindowed packed kernels, bit for bit.  out / lse:
+    optional dense buffers [T_q, H, D] / fp32 [H, T_q] to write into (rows no sequence covers stay as they were)."""
+    name = "varlen_kvcache_attention_window_forward"
+    left, right = (int(x) for x in window)
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError(f"{name}: rotary_cos and rotary_sin must be given together")
+    if rotary_cos is not None:
+        if k_new is None or v_new is None:
+            raise ValueError(f"{name}: rotary needs new tokens (k_new / v_new)")
+        rope = _rope_args(name, q, rotary_cos, rotary_sin, rotary_interleaved)
+    else:
+        rope = (None, None, _PREC[q.dtype], 0, 0, 0, False)
+    return _varlen_kvcache_forward(name, _lib.umfa_varlen_kvcache_attention_window_forward_stream, (*rope, left, right), q, k_cache, v_cache,
+                                   cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k_new, v_new, scale, causal, num_splits, out_dtype,
+                                   out, lse)
+
+
 def varlen_kvcache_item_counts(device=None):
     """(decode-form items, 128-row items) the last varlen_kvcache_attention_forward (16-bit or fp8) on torch's current stream ran, counted by the
     kernel (umfa_varlen_kvcache_item_counts).  Debug: synchronises the stream."""
