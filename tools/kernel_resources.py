@@ -53,7 +53,7 @@ def main():
             g = re.search(key + r":\s+(\d+)", entry)
             return int(g.group(1)) if g else -1
         k0 = text.index("\n" + name + ":")
-        body = text[k0:text.index("s_endpgm", k0)]
+        body = text[k0:text.index("\n.Lfunc_end", k0)]  # (the whole function: a kernel with an early exit holds more than one s_endpgm)
         dem = name if a.mangled else subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         vgpr, lds = get(r'.vgpr_count'), get(r'.group_segment_fixed_size') + a.dyn_lds
         waves = min(8, 512 // (8 * max(1, -(-vgpr // 8))))

@@ -1,12 +1,17 @@
-// fa_paged_device.h -- the device pieces the five KV-cache forwards share (fa_fwd_16_paged.hip, fa_fwd_16_paged_window.hip,
-// fa_fwd_16_paged_varlen.hip, fa_fwd_16_paged_fp8.hip, fa_fwd_16_paged_varlen_fp8.hip).  Every kernel keeps its own shell -- parameters,
-// item and row mapping, key range and split, step loop, staging scheme and barriers -- and calls these leaves; what differs between the
-// kernels (the mask predicate, the destination rows) comes in as an always-inline callable or a plain argument.  Each translation unit
-// gets its own copy (internal linkage), as with fa_paged_fp8.h's pieces of the fp8 stage ring.
+// fa_paged_device.h -- the device leaves the six KV-cache forwards share: the plain, fp8 and sliding-window kernels, each in a dense form
+// (fa_fwd_16_paged.hip, fa_fwd_16_paged_fp8.hip, fa_fwd_16_paged_window.hip) and a packed one (fa_fwd_16_paged_varlen.hip,
+// fa_fwd_16_paged_varlen_fp8.hip, fa_fwd_16_paged_varlen_window.hip).  What differs between the callers (the mask predicate, the
+// destination rows) comes in as an always-inline callable, an item (fa_paged_item.h) or a plain argument.  Each translation unit gets
+// its own copy (internal linkage), as with fa_paged_fp8.h's pieces of the fp8 stage ring.
 //
-// paged_tile is called by four of the five: fa_fwd_16_paged_varlen.hip keeps the same step in place, because the shared function cost
-// that kernel alone 1.5 % of its time (profiles/paged_shared/summary.md).  A change to one of the two must be made to the other: the
-// packed kernels' bitwise agreement with the plain ones at equal lengths (tests/test_gpu_varlen_paged.py) fails otherwise.
+// Above the leaves, the two sliding-window kernels are one body (fa_paged_window_body.h) over the dense or the packed item.  The plain
+// and the fp8 kernels keep their own shells -- parameters, item and row mapping, key range and split, step loop, staging scheme and
+// barriers -- in a dense and a packed copy each, which must be edited in step: the packed kernels' bitwise agreement with the dense
+// ones at equal lengths (tests/test_gpu_varlen_paged.py, tests/test_gpu_varlen_paged_fp8.py) fails otherwise.  One body for each of
+// those pairs was built and measured: same registers, same loop, 0.5 - 2.5 % slower (profiles/paged_body/summary.md).
+//
+// paged_tile is called by five of the six: fa_fwd_16_paged_varlen.hip keeps the same step in place, because the shared function cost
+// that kernel alone 1.5 % of its time (profiles/paged_shared/summary.md).  A change to one of the two must be made to the other.
 //
 // The workgroup: 4 waves x 32 query rows, S^T = K Q^T so a lane owns one query (ql = lane & 31) and one half of the subtile's keys
 // (hi = lane >> 5); the exact running max is shared by the two halves, P V runs in fp16.  A step is 128 keys of K and of V: four 32-key
@@ -22,8 +27,8 @@
 // bf16 V (the 16-bit caches): the tile lands as bf16 and every wave converts the V pieces its own DMA filled to fp16 in place
 // (v * 2^-e), keeping the largest |v| it saw (paged_convert_v).  Behind the loop the 128-row kernel's range rule decides
 // (fa_fwd_16_kernel.h v_range_check): outputs non-finite, or rows with keys and every output below 2^-11, sweep this workgroup's keys
-// once more with e from that largest |v|; the outputs are shifted back.  The rule itself stays in the three 16-bit kernels: as a shared
-// function it cost each bf16 kernel 4 to 10 scalar registers, up to a spill (profiles/paged_shared/resources.md).
+// once more with e from that largest |v|; the outputs are shifted back.  The rule itself stays in the 16-bit kernels and the window
+// body: as a shared function it cost each bf16 kernel 4 to 10 scalar registers, up to a spill (profiles/paged_shared/resources.md).
 #pragma once
 #include <type_traits>
 
@@ -245,6 +250,18 @@ __device__ __forceinline__ void paged_store_out(void* out, int64_t orow, float* 
             }
         }
     if (hi == 0 && lse) lse[lse_at] = L > 0.0f ? (m + __builtin_log2f(L)) * UMFA_LN2 : -INFINITY;
+}
+
+// row r (query token qi, head h) of item `it` (fa_paged_item.h), scaled by f: a split-KV part's row when OUT is void, else the final row
+template <int DP, typename OUT, typename ITEM>
+__device__ __forceinline__ void paged_store_row(const PagedParams& p, const ITEM& it, uint32_t r, uint32_t qi, uint32_t h,
+                                                const f32x16 (&acc)[DP / 32], float f, float m, float L, int hi) {
+    if constexpr (std::is_same<OUT, void>::value) {
+        const int64_t rows_all = it.part_rows();
+        paged_store_part<DP>(p.part, (int64_t)p.nsplit * rows_all, (int64_t)it.part * rows_all + it.part_row(r), acc, f, m, L, hi);
+    } else {
+        paged_store_out<DP, OUT>(p.out, it.o_row(qi, h) * DP, p.lse, it.lse_at(qi, h), acc, f, m, L, hi);
+    }
 }
 
 }  // namespace

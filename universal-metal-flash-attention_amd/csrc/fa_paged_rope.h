@@ -45,6 +45,12 @@ struct RopeArgs {
     bool interleaved;
 };
 
+// an entry's rotary arguments; table_fp32 / table_operand: rotary_table_precision is fp32 / is the call's input_precision
+inline RopeArgs paged_rope_args(const void* cos, const void* sin, bool table_fp32, bool table_operand, int64_t row_stride, uint32_t seqlen_ro,
+                                uint32_t rotary_dim, bool interleaved) {
+    return RopeArgs{cos, sin, table_fp32 ? 1 : table_operand ? 0 : -1, row_stride, seqlen_ro, rotary_dim, interleaved};
+}
+
 // r's table fields from the entry's arguments (everything else of r is the runtime's)
 inline void paged_rope_fill(PagedRopeParams& r, const RopeArgs& a) {
     r.cos = a.cos; r.sin = a.sin; r.rstride = a.row_stride; r.seqlen_ro = a.seqlen_ro; r.rdim = a.rotary_dim;

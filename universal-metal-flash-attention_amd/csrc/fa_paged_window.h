@@ -20,6 +20,8 @@ struct PagedWindowParams {
 };
 
 bool paged_window_supported(const PagedWindowParams& w);
+// the bounds' part of it, which the packed form (fa_paged_varlen_window.h) shares: capacity and p.Sq below 2^30, each side normalised
+bool paged_window_bounds_ok(const PagedParams& p, int left, int right);
 // the append and (split) the fold are fa_paged.h's launch_paged_append / launch_paged_fold; this launches the attention and the fold
 hipError_t launch_fwd_16_paged_window(const PagedWindowParams& w, hipStream_t stream, const char** name);
 

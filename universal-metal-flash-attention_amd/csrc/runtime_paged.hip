@@ -8,69 +8,13 @@
 // MFA_ERROR_MEMORY_ALLOCATION: warm up first).  Anything outside the kernels' scope is MFA_ERROR_INVALID_ARGS: no silent fall-back.
 #include <string.h>
 
-#include "runtime_internal.h"
+#include "runtime_paged_common.h"
 #include "fa_paged_fp8.h"
 #include "fa_paged_rope.h"
 #include "fa_paged_window.h"
 
 using namespace umfa;
 using namespace umfa_rt;
-
-namespace {
-
-mfa_error_t rc_paged(hipError_t e) {
-    return e == hipSuccess ? MFA_SUCCESS : e == hipErrorInvalidValue ? MFA_ERROR_INVALID_ARGS
-                                         : e == hipErrorOutOfMemory ? MFA_ERROR_MEMORY_ALLOCATION : MFA_ERROR_EXECUTION_FAILED;
-}
-
-int paged_cu_count(int dev) {
-    static int cached[64] = {0};
-    if (dev < 0 || dev >= 64) return 256;
-    if (!cached[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-            (void)hipGetLastError();
-            n = 256;
-        }
-        cached[dev] = n;
-    }
-    return cached[dev];
-}
-
-// split-KV parts when the caller leaves it to the library: enough workgroups for every CU's slots (one workgroup per CU at head_dim 128,
-// two at 64), each part at least two 128-key steps of the capacity, at most 64 parts
-uint32_t paged_auto_splits(const PagedParams& p, int ncu) {
-    const uint64_t items = (uint64_t)p.B * p.Hkv * p.nrb;
-    const uint64_t slots = (uint64_t)ncu * (p.D == 128 ? 1 : 2);
-    if (items >= slots) return 1;
-    uint64_t n = (slots + items - 1) / items;
-    const uint64_t steps = ((uint64_t)p.max_pages * p.page_size + 127) / 128;
-    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
-    n = n < by_len ? n : by_len;
-    return (uint32_t)(n < 64 ? n : 64);
-}
-
-// the band of a window call, normalised by the entry: each side a bound that binds or PAGED_WIN_OPEN
-struct WindowArgs {
-    int left, right;
-};
-
-// paged_auto_splits' rule with the length capped by the band instead of the capacity: a workgroup visits the steps of at most
-// left + right + Sq keys (an open side: the capacity), plus one step for a band that straddles a step boundary
-uint32_t paged_window_auto_splits(const PagedParams& p, const WindowArgs& w, int ncu) {
-    const uint64_t items = (uint64_t)p.B * p.Hkv * p.nrb;
-    const uint64_t slots = (uint64_t)ncu * (p.D == 128 ? 1 : 2);
-    if (items >= slots) return 1;
-    uint64_t n = (slots + items - 1) / items;
-    const uint64_t cap = (uint64_t)p.max_pages * p.page_size;
-    const uint64_t band = (w.left == PAGED_WIN_OPEN ? cap : (uint64_t)w.left) + (w.right == PAGED_WIN_OPEN ? cap : (uint64_t)w.right) + p.Sq;
-    const uint64_t steps = ((band < cap ? band : cap) + 127) / 128 + 1;
-    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
-    n = n < by_len ? n : by_len;
-    return (uint32_t)(n < 64 ? n : 64);
-}
-
-}  // namespace
 
 namespace {
 
@@ -139,8 +83,7 @@ mfa_error_t kvcache_forward(mfa_context_t context, void* stream, const void* q, 
     const int dev = stream_device((hipStream_t)stream);
     DeviceGuard guard(dev);
     p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256)
-               : win          ? paged_window_auto_splits(p, *win, paged_cu_count(dev))
-                              : paged_auto_splits(p, paged_cu_count(dev));
+                              : paged_auto_splits(p, (uint64_t)p.B * p.Hkv * p.nrb, win, paged_cu_count(dev));
     if (!supported()) return MFA_ERROR_INVALID_ARGS;
     if (rope) {
         // one block of the pooled workspace: the rotated q image, then (split) the partials; every check and the allocation come before
@@ -209,11 +152,9 @@ mfa_error_t umfa_kvcache_attention_fp8_forward_stream(mfa_context_t context, voi
                                                       int32_t input_precision, void* out, int32_t out_precision, float* lse,
                                                       int32_t num_splits, const float* k_descale, const int64_t* k_descale_strides,
                                                       const float* v_descale, const int64_t* v_descale_strides) {
-    if (!k_descale || !v_descale || !k_descale_strides || !v_descale_strides) return MFA_ERROR_INVALID_ARGS;
     PagedFp8Params f8;
     memset(&f8, 0, sizeof(f8));
-    f8.kd = k_descale; f8.kdb = k_descale_strides[0]; f8.kdh = k_descale_strides[1];
-    f8.vd = v_descale; f8.vdb = v_descale_strides[0]; f8.vdh = v_descale_strides[1];
+    if (!paged_fill_descales(f8, k_descale, k_descale_strides, v_descale, v_descale_strides)) return MFA_ERROR_INVALID_ARGS;
     return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,
                            v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
                            num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
@@ -237,14 +178,12 @@ mfa_error_t umfa_kvcache_attention_rope_forward_stream(mfa_context_t context, vo
     PagedFp8Params f8;
     memset(&f8, 0, sizeof(f8));
     if (cache_fp8) {
-        if (!k_descale || !v_descale || !k_descale_strides || !v_descale_strides) return MFA_ERROR_INVALID_ARGS;
-        f8.kd = k_descale; f8.kdb = k_descale_strides[0]; f8.kdh = k_descale_strides[1];
-        f8.vd = v_descale; f8.vdb = v_descale_strides[0]; f8.vdh = v_descale_strides[1];
+        if (!paged_fill_descales(f8, k_descale, k_descale_strides, v_descale, v_descale_strides)) return MFA_ERROR_INVALID_ARGS;
     } else if (k_descale || v_descale || k_descale_strides || v_descale_strides) {
         return MFA_ERROR_INVALID_ARGS;
     }
-    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
-    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    const RopeArgs rope = paged_rope_args(rotary_cos, rotary_sin, rotary_table_precision == MFA_PRECISION_FP32,
+                                          rotary_table_precision == input_precision, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
     return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,
                            v_new_strides, block_table, block_table_stride, cache_seqlens, batch, seqlen_q, seqlen_new, num_heads,
                            num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq, softmax_scale, causal, input_precision, out,
@@ -269,17 +208,12 @@ mfa_error_t umfa_kvcache_attention_window_forward_stream(mfa_context_t context, 
     if (cache_fp8 || k_descale || v_descale || k_descale_strides || v_descale_strides) return MFA_ERROR_INVALID_ARGS;
     if (window_left < -1 || window_right < -1) return MFA_ERROR_INVALID_ARGS;
     if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
-    // the window, normalised once: causal is right = 0; a side that cannot bind (left >= capacity, right >= Sq) is open
     const uint64_t cap = block_table ? (uint64_t)max_pages_per_seq * page_size : (uint64_t)page_size;
     if (cap >= (1ull << 30)) return MFA_ERROR_INVALID_ARGS;
-    if (causal) window_right = 0;
-    WindowArgs w;
-    w.left = window_left < 0 || (uint64_t)window_left >= cap ? PAGED_WIN_OPEN : window_left;
-    w.right = window_right < 0 || (uint32_t)window_right >= seqlen_q ? PAGED_WIN_OPEN : window_right;
-    // a window that bounds nothing (or only as causal does): the unwindowed kernels, unchanged
-    const bool plain = w.left == PAGED_WIN_OPEN && (w.right == PAGED_WIN_OPEN || (causal && w.right == 0));
-    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
-    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    bool plain;
+    const WindowArgs w = paged_window_normalise(window_left, window_right, causal, cap, seqlen_q, plain);
+    const RopeArgs rope = paged_rope_args(rotary_cos, rotary_sin, rotary_table_precision == MFA_PRECISION_FP32,
+                                          rotary_table_precision == input_precision, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
     PagedFp8Params f8;
     memset(&f8, 0, sizeof(f8));
     return kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides, v_new,

@@ -9,7 +9,7 @@
 // outside the kernels' scope is MFA_ERROR_INVALID_ARGS: no silent fall-back.
 #include <string.h>
 
-#include "runtime_internal.h"
+#include "runtime_paged_common.h"
 #include "fa_paged_varlen.h"
 #include "fa_paged_rope.h"
 #include "fa_paged_varlen_fp8.h"
@@ -19,55 +19,6 @@ using namespace umfa;
 using namespace umfa_rt;
 
 namespace {
-
-mfa_error_t rc_pv(hipError_t e) {
-    return e == hipSuccess ? MFA_SUCCESS : e == hipErrorInvalidValue ? MFA_ERROR_INVALID_ARGS
-                                         : e == hipErrorOutOfMemory ? MFA_ERROR_MEMORY_ALLOCATION : MFA_ERROR_EXECUTION_FAILED;
-}
-
-int pv_cu_count(int dev) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        n = 256;
-    }
-    return n;
-}
-
-// split-KV parts when the caller leaves it to the library: kvcache_attention's rule (runtime_paged.hip) on the item bound -- enough
-// workgroups for every CU's slots (one per CU at head_dim 128, two at 64), each part at least two 128-key steps of the capacity, at
-// most 64 parts.  With every L_q equal the bound is the existing entry's item count, so both entries choose the same.
-uint32_t pv_auto_splits(const PagedVarlenParams& v, int ncu) {
-    const uint64_t items = v.n_items;
-    const uint64_t slots = (uint64_t)ncu * (v.p.D == 128 ? 1 : 2);
-    if (items == 0 || items >= slots) return 1;
-    uint64_t n = (slots + items - 1) / items;
-    const uint64_t steps = ((uint64_t)v.p.max_pages * v.p.page_size + 127) / 128;
-    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
-    n = n < by_len ? n : by_len;
-    return (uint32_t)(n < 64 ? n : 64);
-}
-
-// the band of a window call, normalised by the entry: each side a bound that binds or PAGED_WIN_OPEN
-struct PvWindowArgs {
-    int left, right;
-};
-
-// pv_auto_splits' rule with the length capped by the band instead of the capacity, as kvcache_window_attention caps it
-// (runtime_paged.hip paged_window_auto_splits): an item visits the steps of at most left + right + max_seqlen_q keys (an open side: the
-// capacity), plus one step for a band that straddles a step boundary.  With every L_q equal both entries choose the same.
-uint32_t pv_window_auto_splits(const PagedVarlenParams& v, const PvWindowArgs& w, int ncu) {
-    const uint64_t items = v.n_items;
-    const uint64_t slots = (uint64_t)ncu * (v.p.D == 128 ? 1 : 2);
-    if (items == 0 || items >= slots) return 1;
-    uint64_t n = (slots + items - 1) / items;
-    const uint64_t cap = (uint64_t)v.p.max_pages * v.p.page_size;
-    const uint64_t band = (w.left == PAGED_WIN_OPEN ? cap : (uint64_t)w.left) + (w.right == PAGED_WIN_OPEN ? cap : (uint64_t)w.right) + v.p.Sq;
-    const uint64_t steps = ((band < cap ? band : cap) + 127) / 128 + 1;
-    const uint64_t by_len = steps / 2 ? steps / 2 : 1;
-    n = n < by_len ? n : by_len;
-    return (uint32_t)(n < 64 ? n : 64);
-}
 
 constexpr size_t PV_HDR_B = 256;  // the tally's words at the front of the workspace block
 
@@ -87,7 +38,7 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
                                    uint32_t num_kv_heads, uint16_t head_dim, uint32_t page_size, uint32_t num_pages,
                                    uint32_t max_pages_per_seq, float softmax_scale, bool causal, int32_t input_precision, void* out,
                                    int32_t out_precision, float* lse, int32_t num_splits, const RopeArgs* rope,
-                                   const PagedVarlenFp8Params* f8 = nullptr, const PvWindowArgs* win = nullptr) {
+                                   const PagedVarlenFp8Params* f8 = nullptr, const WindowArgs* win = nullptr) {
     Context* ctx = as_ctx(context);
     if (win && f8) return MFA_ERROR_INVALID_ARGS;
     if (rope && (!has_new || !rope->cos || !rope->sin || rope->table_f32 < 0))
@@ -141,9 +92,8 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
     std::lock_guard<std::mutex> lock(ctx->mu);
     const int dev = stream_device((hipStream_t)stream);
     DeviceGuard guard(dev);
-    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256)
-               : win          ? pv_window_auto_splits(v, *win, pv_cu_count(dev))
-                              : pv_auto_splits(v, pv_cu_count(dev));
+    // (automatic: kvcache_attention's rule on the item bound -- runtime_paged_common.h)
+    p.nsplit = num_splits > 0 ? (uint32_t)(num_splits < 256 ? num_splits : 256) : paged_auto_splits(p, v.n_items, win, paged_cu_count(dev));
     if (!supported()) return MFA_ERROR_INVALID_ARGS;
     PagedRopeParams r;
     memset(&r, 0, sizeof(r));
@@ -178,20 +128,20 @@ mfa_error_t varlen_kvcache_forward(mfa_context_t context, void* stream, const vo
                 if (!paged_rope_supported(r)) return MFA_ERROR_INVALID_ARGS;
                 e = launch_paged_rope(r, (hipStream_t)stream);
             }
-            if (e != hipSuccess) return rc_pv(e);
+            if (e != hipSuccess) return rc_paged(e);
             p.q = r.qimg;
             p.qst = (int64_t)num_heads * head_dim; p.qsh = head_dim;
         }
     } else if (has_new) {
         const hipError_t e = f8 ? launch_paged_varlen_fp8_append(f, (hipStream_t)stream) : launch_paged_varlen_append(v, (hipStream_t)stream);
-        if (e != hipSuccess) return rc_pv(e);
+        if (e != hipSuccess) return rc_paged(e);
     }
     // (v as it stands here: the rotary path has pointed p.q at its image by now)
     const hipError_t e = f8    ? launch_fwd_16_paged_varlen_fp8(f, (hipStream_t)stream, &name)
                          : win ? launch_fwd_16_paged_varlen_window(PagedVarlenWindowParams{v, win->left, win->right}, (hipStream_t)stream, &name)
                                : launch_fwd_16_paged_varlen(v, (hipStream_t)stream, &name);
     ctx->last_kernel = name;
-    return rc_pv(e);
+    return rc_paged(e);
 }
 
 }  // namespace
@@ -221,8 +171,8 @@ mfa_error_t umfa_varlen_kvcache_attention_rope_forward_stream(
     int32_t input_precision, void* out, int32_t out_precision, float* lse, int32_t num_splits, const void* rotary_cos,
     const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
     bool rotary_interleaved) {
-    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
-    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    const RopeArgs rope = paged_rope_args(rotary_cos, rotary_sin, rotary_table_precision == MFA_PRECISION_FP32,
+                                          rotary_table_precision == input_precision, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
     return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
                                   v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
                                   cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
@@ -239,14 +189,12 @@ mfa_error_t umfa_varlen_kvcache_attention_fp8_forward_stream(
     const int64_t* k_descale_strides, const float* v_descale, const int64_t* v_descale_strides, const void* rotary_cos,
     const void* rotary_sin, int32_t rotary_table_precision, int64_t rotary_row_stride, uint32_t seqlen_ro, uint32_t rotary_dim,
     bool rotary_interleaved) {
-    if (!k_descale || !v_descale || !k_descale_strides || !v_descale_strides) return MFA_ERROR_INVALID_ARGS;
-    if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
     PagedVarlenFp8Params f8;
     memset(&f8, 0, sizeof(f8));
-    f8.kd = k_descale; f8.kdb = k_descale_strides[0]; f8.kdh = k_descale_strides[1];
-    f8.vd = v_descale; f8.vdb = v_descale_strides[0]; f8.vdh = v_descale_strides[1];
-    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
-    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    if (!paged_fill_descales(f8, k_descale, k_descale_strides, v_descale, v_descale_strides)) return MFA_ERROR_INVALID_ARGS;
+    if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
+    const RopeArgs rope = paged_rope_args(rotary_cos, rotary_sin, rotary_table_precision == MFA_PRECISION_FP32,
+                                          rotary_table_precision == input_precision, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
     return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
                                   v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
                                   cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
@@ -265,17 +213,12 @@ mfa_error_t umfa_varlen_kvcache_attention_window_forward_stream(
     bool rotary_interleaved, int32_t window_left, int32_t window_right) {
     if (window_left < -1 || window_right < -1) return MFA_ERROR_INVALID_ARGS;
     if ((rotary_cos == nullptr) != (rotary_sin == nullptr)) return MFA_ERROR_INVALID_ARGS;
-    // the window, normalised once: causal is right = 0; a side that cannot bind (left >= capacity, right >= max_seqlen_q) is open
     const uint64_t cap = block_table ? (uint64_t)max_pages_per_seq * page_size : (uint64_t)page_size;
     if (cap >= (1ull << 30) || max_seqlen_q >= (1u << 30)) return MFA_ERROR_INVALID_ARGS;
-    if (causal) window_right = 0;
-    PvWindowArgs w;
-    w.left = window_left < 0 || (uint64_t)window_left >= cap ? PAGED_WIN_OPEN : window_left;
-    w.right = window_right < 0 || (uint32_t)window_right >= max_seqlen_q ? PAGED_WIN_OPEN : window_right;
-    // a window that bounds nothing (or only as causal does): the unwindowed packed kernels, unchanged
-    const bool plain = w.left == PAGED_WIN_OPEN && (w.right == PAGED_WIN_OPEN || (causal && w.right == 0));
-    const int tf32 = rotary_table_precision == MFA_PRECISION_FP32 ? 1 : rotary_table_precision == input_precision ? 0 : -1;  // -1: refused
-    const RopeArgs rope = {rotary_cos, rotary_sin, tf32, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved};
+    bool plain;
+    const WindowArgs w = paged_window_normalise(window_left, window_right, causal, cap, max_seqlen_q, plain);
+    const RopeArgs rope = paged_rope_args(rotary_cos, rotary_sin, rotary_table_precision == MFA_PRECISION_FP32,
+                                          rotary_table_precision == input_precision, rotary_row_stride, seqlen_ro, rotary_dim, rotary_interleaved);
     return varlen_kvcache_forward(context, stream, q, q_strides, k_cache, k_cache_strides, v_cache, v_cache_strides, k_new, k_new_strides,
                                   v_new, v_new_strides, block_table, block_table_stride, cache_seqlens, total_q, batch, max_seqlen_q,
                                   cu_seqlens_q, has_new, num_heads, num_kv_heads, head_dim, page_size, num_pages, max_pages_per_seq,
